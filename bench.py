@@ -1,15 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- EM hot-path benchmark on MI355X (contract: see the task statement / DESIGN.md section 6).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--legs C2[,C5]] [--kernel 0..3]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--kernel 0..3] [--dump-outputs DIR] [--full [--legs C2[,C5]] ...]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one EM round (E step + M step, EM.cpp:365-416 with frozen CSR values) over the whole read x transcript
 matrix of BASELINE.json configs[2] (the configuration the north-star target is quoted on: PairedEndQModel-shaped,
 50 M reads, 200 k transcripts, ~10 alignments per read; `--config` C2 / C5 select configs[1] / configs[4]), synthetic
 and seeded (tools/synth_data.py), resident in HBM before the timed region.  value = read-alignments processed per
-second = nnz * rounds / wall.  The timed region is repeated (K rounds each time, bracketed by a barrier and a device
-synchronisation on both sides) until at least 0.5 s have been measured, whatever K is; ms_per_step is the mean.
+second = nnz * rounds / wall.  After W untimed rounds, the timed region is exactly K rounds (one rsem_em_run call,
+bracketed by a barrier and a device synchronisation on both sides); ms_per_step is its wall time / K.
+--dump-outputs DIR: what that call handed back after the K-th round (theta and the fractional counts, M+1 doubles each)
+as DIR/theta.npy and DIR/counts.npy; the inputs are seeded, so two builds compare output for output.
+A plain run does only that and prints the contract keys.  --full adds everything else beside the headline: the E-step launch
+times and roofline, the one-step parity check against the CPU restatement, the Q32 leg, the other configs' legs, Gibbs,
+credibility intervals, the reference binary's CPU baseline and whole-program wall clocks, and the full record in
+profiles/bench_detail_latest.json.
 N > 1: weak scaling -- every rank holds its own config-sized shard of reads over the same transcriptome, theta
 replicated, one RCCL all-reduce of the M+1 fractional counts per round, issued from C++ on the kernel stream
 (rsem_em_set_comm; the communicator id travels through torch.distributed); the Gibbs leg deals independent chains to the
@@ -416,9 +422,39 @@ def ci_leg(capi, M, nCV=1000, nSpC=50):
         return {"error": str(e)}
 
 
+def headline_steps(ctx, wl, N0, K, W, sync, barrier):
+    """W untimed rounds, then exactly K timed rounds in one region (barrier + device sync on both sides).  Returns (elapsed_s, out),
+    out = what rsem_em_run handed its caller after the K-th round."""
+    if W > 0:
+        ctx.run(wl["theta0"], N0, min_round=W, max_round=W)
+    barrier()
+    sync()
+    t0 = time.perf_counter()
+    out = ctx.run(wl["theta0"], N0, min_round=K, max_round=K)
+    sync()
+    barrier()
+    elapsed = time.perf_counter() - t0
+    assert out["rounds"] == K
+    return elapsed, out
+
+
+def launch_ms(ctx, wl, N0, K):
+    """The average E-step launch time of one more min(K, 64)-round region, HIP events around every launch."""
+    prof = ctx.run(wl["theta0"], N0, min_round=min(K, 64), max_round=min(K, 64), profile=True)["profile"]
+    return prof.estep_ms_sum / max(prof.estep_launches, 1)
+
+
+def dump_outputs(d, out):
+    """--dump-outputs DIR: theta and the fractional counts rsem_em_run returned after the last timed round, as float64 .npy files."""
+    os.makedirs(d, exist_ok=True)
+    for k in ("theta", "counts"):
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(out[k], np.float64))
+
+
 def timed_rounds(ctx, wl, N0, K, W, sync, barrier, agree=lambda x: x):
-    """W untimed rounds, then K-round regions (barrier + device sync on both sides) until MIN_TIMED_S is covered; then one
-    more K-round region with HIP events around every E-step launch.  Returns (elapsed_s, rounds, reps, estep_ms, theta_sum)."""
+    """The side legs' procedure (--full): W untimed rounds, then K-round regions (barrier + device sync on both sides) until
+    MIN_TIMED_S is covered; then one more K-round region with HIP events around every E-step launch.  Returns (elapsed_s, rounds,
+    reps, estep_ms, theta_sum)."""
     if W > 0:
         ctx.run(wl["theta0"], N0, min_round=W, max_round=W)
     elapsed, reps = 0.0, 0
@@ -434,9 +470,7 @@ def timed_rounds(ctx, wl, N0, K, W, sync, barrier, agree=lambda x: x):
         assert out["rounds"] == K
         if agree(elapsed) >= MIN_TIMED_S or reps >= 4096:  # agree(): the same decision on every rank (max over ranks)
             break
-    prof = ctx.run(wl["theta0"], N0, min_round=min(K, 64), max_round=min(K, 64), profile=True)["profile"]
-    estep_ms = prof.estep_ms_sum / max(prof.estep_launches, 1)
-    return elapsed, reps * K, reps, estep_ms, float(out["theta"].sum())
+    return elapsed, reps * K, reps, launch_ms(ctx, wl, N0, K), float(out["theta"].sum())
 
 
 def q32_leg(ctx, wl, N0, K, W, sync, alg_bytes, f64_ms_per_step, f64_estep_ms, traffic=None):
@@ -713,17 +747,24 @@ def main():
     ap.add_argument("--gibbs-sweeps", type=int, default=30)
     ap.add_argument("--no-bam-leg", action="store_true", help="skip the -b (transcript.bam) leg of the end-to-end comparison")
     ap.add_argument("--gibbs-exact-rounds", type=int, default=6, help="rounds of the exact (reference) chain timed in the Gibbs leg (>= 2)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write theta and counts of the last timed round as DIR/theta.npy, DIR/counts.npy (float64)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline (roofline, parity, Q32, "
+                    "other configs, Gibbs, credibility intervals, reference CPU baseline); the --legs / --no-* options apply to it")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # called without a launcher: start one rank per GPU ourselves (the contract's launch line)
+        # called without a launcher: start one rank per GPU ourselves (the contract's launch line), in a child process
+        import subprocess
         port = os.environ.get("MASTER_PORT", str(29500 + os.getpid() % 2000))
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
                "--master-addr", "127.0.0.1", "--master-port", port, os.path.abspath(__file__)] + sys.argv[1:]
         if os.environ.get("BENCH_PRINT_LAUNCH"):  # (tests: show the launch line instead of running it)
             print(json.dumps(cmd))
             return
-        os.execv(sys.executable, cmd)
+        rc = subprocess.call(cmd)
+        sys.exit(rc if rc >= 0 else 128 - rc)
 
     # stdout carries exactly one JSON line: libraries that print to the C-level stdout (RCCL's version banner) are sent to
     # stderr for the whole run, the line itself goes to the saved descriptor at the end
@@ -792,24 +833,50 @@ def main():
     if comm is not None:
         ctx.set_comm(comm)
     N0g = float(wl["N0"] * world)  # every rank passes the GLOBAL N0 (rsem_em_set_comm)
-    def agree(x):
-        if not distributed:
-            return x
-        t = torch.tensor([x], dtype=torch.float64, device=tdev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        return float(t.item())
 
-    elapsed, rounds, reps, estep_ms, theta_sum = timed_rounds(ctx, wl, N0g, K, W, sync, barrier, agree)
+    def finish():
+        if comm is not None:
+            barrier()
+            comm.close()
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    elapsed, out = headline_steps(ctx, wl, N0g, K, W, sync, barrier)
+    rounds, theta_sum = K, float(out["theta"].sum())
     total_nnz = nnz
+    if distributed:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=tdev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+        tn = torch.tensor([float(nnz)], dtype=torch.float64, device=tdev)
+        dist.all_reduce(tn)
+        total_nnz = int(tn.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
+    headline = {
+        "metric": "EM read-alignments/s (nnz x EM iterations per second), rsem-run-em theta-only rounds",
+        "value": total_nnz * rounds / elapsed, "unit": "read-alignments/s",
+        "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": elapsed * 1e3 / rounds,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "em_iterations_per_s": rounds / elapsed, "timed_rounds": rounds, "timed_region_s": elapsed,
+        "config": {"workload": "%s: EM matrix of %d reads x %d transcripts, %d alignments (%.2f/read) per GPU, frozen conprb "
+                               "(rounds >= 12)" % (WORKLOADS.get(args.config, args.config), N1, M, nnz, nnz / max(N1, 1)),
+                   "synthetic_config": args.config, "kernel": args.kernel, "value_bits": args.value_bits,
+                   "parallelism": "1 GPU" if world == 1 else "read-sharded x%d + RCCL all-reduce(M+1 f64)/round from C++ on the EM stream" % world},
+        "upload_and_layout_s": upload_s,
+    }
+    if not args.full:
+        ctx.close()
+        if rank == 0:
+            os.write(json_fd, (json.dumps(_num(headline), separators=(",", ":")) + "\n").encode())
+        finish()
+        return
+
+    estep_ms = launch_ms(ctx, wl, N0g, K)
     dist_info = None
     if distributed:
         dev = tdev
-        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-        tn = torch.tensor([float(nnz)], dtype=torch.float64, device=dev)
-        dist.all_reduce(tn)
-        total_nnz = int(tn.item())
         # per-rank E-step time and the cost of the per-round collective alone (same size, same communicator)
         es = torch.zeros(world, 2, dtype=torch.float64, device=dev)
         es[rank, 0] = estep_ms
@@ -937,18 +1004,9 @@ def main():
             except Exception as e:
                 stream = {"error": str(e)}
         phys_achieved = (phys_headline.get("frac_physical") or 0.0) * HBM_PEAK_GBPS
-        line = {
-            "metric": "EM read-alignments/s (nnz x EM iterations per second), rsem-run-em theta-only rounds",
-            "value": total_nnz * rounds / elapsed, "unit": "read-alignments/s",
-            "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": elapsed * 1e3 / rounds,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "em_iterations_per_s": rounds / elapsed, "timed_rounds": rounds, "timed_region_s": elapsed, "timed_repeats_of_steps": reps,
-            "config": {"workload": "%s: EM matrix of %d reads x %d transcripts, %d alignments (%.2f/read) per GPU, frozen conprb "
-                                   "(rounds >= 12)" % (WORKLOADS.get(args.config, args.config), N1, M, nnz, nnz / max(N1, 1)),
-                       "synthetic_config": args.config, "kernel": args.kernel, "value_bits": args.value_bits,
-                       "value_plane_bytes": value_plane_bytes,
-                       "units_with_ids_outside_their_window": units_far,
-                       "parallelism": "1 GPU" if world == 1 else "read-sharded x%d + RCCL all-reduce(M+1 f64)/round from C++ on the EM stream" % world},
+        line = dict(headline)
+        line["config"] = dict(headline["config"], value_plane_bytes=value_plane_bytes, units_with_ids_outside_their_window=units_far)
+        line.update({
             "roofline": {"bound": "hbm", "achieved": phys_achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": phys_achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_src,
                          "kernel": "k_estep_lane (E step)", "algorithmic_bytes_per_launch": alg_bytes,
@@ -970,9 +1028,8 @@ def main():
                          "traffic_rate_over_stream_read": (traffic / (estep_ms * 1e-3) / 1e9 / stream["read_GBps"])
                          if traffic and stream and stream.get("read_GBps") else None},
             "checks": {"theta_sum": theta_sum, "parity_one_step": parity},
-            "upload_and_layout_s": upload_s,
             "gibbs": gibbs,
-        }
+        })
         if q32 is not None:
             line["q32_value_planes"] = q32
         if dist_info:
@@ -1007,12 +1064,7 @@ def main():
             except Exception:
                 pass
         os.write(json_fd, (contract_line(line, write_detail(line)) + "\n").encode())
-    if comm is not None:
-        barrier()
-        comm.close()
-    if distributed:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

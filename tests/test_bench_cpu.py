@@ -22,7 +22,7 @@ class Prof: estep_ms_sum = 2.0; estep_launches = 2
 class FakeCtx:
     def __init__(self, M, rp, sid, cp=None, ncp=None, device=0): self.opts = {"value_bits": 64}
     def run(self, th, N0, round0=0, min_round=1, max_round=1, profile=False):
-        out = dict(theta=np.array(th, float) / np.sum(th), rounds=max_round)
+        out = dict(theta=np.array(th, float) / np.sum(th), rounds=max_round, counts=np.arange(len(th), dtype=float) + max_round)
         if profile: out["profile"] = Prof()
         return out
     def step(self, th, N0):
@@ -73,18 +73,22 @@ capi.gibbs_chain_seeds = lambda seed, n: list(range(n))
 '''
 
 
-def _run_driver(tmp_path, extra="", argv=()):
+def _run_driver(tmp_path, extra="", argv=("--full",)):
     detail = os.path.join(str(tmp_path), "detail.json")
     r = subprocess.run([sys.executable, "-c", DRIVER % {"root": ROOT, "extra": extra, "argv": list(argv)}], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       text=True, timeout=300, env=dict(os.environ, BENCH_DETAIL_PATH=detail))
+                       text=True, timeout=300, env=dict(os.environ, BENCH_DETAIL_PATH=detail, CALLS_PATH=os.path.join(str(tmp_path), "calls.json")))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.split("\n") if l.strip()]
     assert len(lines) == 1, r.stdout[:500]
+    if "--full" not in argv:
+        assert not os.path.exists(detail)
+        return lines[0], json.loads(lines[0]), None
     with open(detail) as f:
         return lines[0], json.loads(lines[0]), json.load(f)
 
 
 def test_bench_main_prints_one_contract_line(tmp_path):
+    """bench.py --full: the headline, the roofline, the side legs and the full record."""
     raw, d, det = _run_driver(tmp_path)
     # the driver keeps the last 8 187 bytes of stdout: the line must fit in them whole (round 5's 22.5 KB line was not parsed)
     assert len(raw) < 8000, len(raw)
@@ -115,6 +119,43 @@ def test_bench_main_prints_one_contract_line(tmp_path):
     for leg in det["other_configs"].values():
         assert leg["frac_physical"] > 0 and leg["physical"]["physical_bytes_per_launch"] == 1500
     assert det["q32_value_planes"]["frac_physical"] == 1020 / 1e-3 / 1e9 / 8000.0
+
+
+# records every rsem_em_run call and every context of a plain run (written at exit)
+PLAIN_EXTRA = r'''
+import atexit, json as _json
+_calls, _ctxs = [], []
+_run, _init = FakeCtx.run, FakeCtx.__init__
+def _rec_run(self, th, N0, round0=0, min_round=1, max_round=1, profile=False):
+    _calls.append([min_round, max_round, profile])
+    return _run(self, th, N0, round0, min_round, max_round, profile)
+def _rec_init(self, *a, **k):
+    _ctxs.append(1)
+    _init(self, *a, **k)
+FakeCtx.run, FakeCtx.__init__ = _rec_run, _rec_init
+capi.stream_probe = boom
+atexit.register(lambda: open(os.environ["CALLS_PATH"], "w").write(_json.dumps({"runs": _calls, "contexts": len(_ctxs)})))
+'''
+
+
+def test_bench_plain_run_times_exactly_the_steps_and_dumps_outputs(tmp_path):
+    """bench.py without --full: one context, W warm-up rounds, then exactly K timed rounds and nothing else; the line holds the
+    contract keys only, no side file; --dump-outputs writes what the last timed call returned."""
+    import numpy as np
+    out = os.path.join(str(tmp_path), "out")
+    raw, d, _ = _run_driver(tmp_path, extra=PLAIN_EXTRA, argv=["--dump-outputs", out])
+    with open(os.path.join(str(tmp_path), "calls.json")) as f:
+        calls = json.load(f)
+    assert calls == {"runs": [[1, 1, False], [3, 3, False]], "contexts": 1}
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["timed_rounds"] == 3 and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert abs(d["ms_per_step"] - d["timed_region_s"] * 1e3 / 3) <= 1e-5 * d["ms_per_step"] + 1e-9
+    for key in ("roofline", "checks", "gibbs", "legs", "cpu_baseline", "ci", "q32", "detail"):
+        assert key not in d, key
+    th, cn = np.load(os.path.join(out, "theta.npy")), np.load(os.path.join(out, "counts.npy"))
+    assert th.dtype == np.float64 and cn.dtype == np.float64 and len(th) == len(cn) > 1
+    assert abs(th.sum() - 1.0) < 1e-12 and np.array_equal(cn, np.arange(len(cn)) + 3.0)  # (the stand-in's counts of a 3-round call)
 
 
 def test_contract_line_of_a_full_run_fits_the_drivers_tail():
@@ -151,7 +192,7 @@ def test_bench_two_ranks_line_carries_per_rank_numbers(tmp_path):
     for rank in range(2):
         env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    BENCH_DIST_BACKEND="gloo", BENCH_DETAIL_PATH=os.path.join(str(tmp_path), "detail%d.json" % rank))
-        code = DRIVER % {"root": ROOT, "extra": DIST_EXTRA, "argv": ["--gpus", "2", "--no-ci"]}
+        code = DRIVER % {"root": ROOT, "extra": DIST_EXTRA, "argv": ["--gpus", "2", "--no-ci", "--full"]}
         procs.append(subprocess.Popen([sys.executable, "-c", code], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=600) for p in procs]
     for p, (o, e) in zip(procs, outs):
@@ -175,7 +216,7 @@ def test_bench_two_ranks_line_carries_per_rank_numbers(tmp_path):
 
 
 def test_bench_starts_its_own_ranks():
-    """`python bench.py --gpus N` without a launcher re-executes itself under torch.distributed.run (one rank per GPU,
+    """`python bench.py --gpus N` without a launcher starts itself under torch.distributed.run in a child (one rank per GPU,
     127.0.0.1); under a launcher whose world size differs from --gpus it refuses."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "7"], env=dict(env, BENCH_PRINT_LAUNCH="1"),

@@ -94,7 +94,7 @@ def test_bench_forced_dist_line_on_one_gpu():
     env = dict(os.environ, BENCH_FORCE_DIST="1", MASTER_PORT="29631", BENCH_DETAIL_PATH=detail_path)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C2", "--scale", "0.1", "--legs=", "--no-cpu-baseline", "--no-ci",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "C2", "--scale", "0.1", "--legs=", "--no-cpu-baseline", "--no-ci",
                         "--steps", "5", "--warmup", "1", "--gibbs-sweeps", "6", "--gibbs-exact-rounds", "2"], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]

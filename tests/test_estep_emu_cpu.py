@@ -26,7 +26,7 @@ BUILDS = {
     "variants": ["-DRSEM_F64_DEPTHS=4,3,3,2", "-DRSEM_Q32_DEPTHS=5,4,3,2", "-DRSEM_FARQ_CAP=260"],
     # the product's body under ThreadSanitizer: one OS thread per lane and pthread barriers for the kernel's barriers, so a report is an
     # LDS / global access of two lanes that no barrier of the kernel orders (None where the toolchain cannot build it)
-    "tsan": ["-fsanitize=thread", "-g"],
+    "tsan": ["-fsanitize=thread", "-fno-gpu-sanitize", "-g"],
 }
 
 

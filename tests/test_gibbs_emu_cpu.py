@@ -16,7 +16,7 @@ import test_estep_emu_cpu as te
 ROOT = te.ROOT
 pytestmark = pytest.mark.skipif(not os.path.exists(te.CC), reason="needs hipcc (host compilation of the HIP headers)")
 
-BUILDS = {"product": [], "tsan": ["-fsanitize=thread", "-g"]}  # (tsan: None where the toolchain cannot build it)
+BUILDS = {"product": [], "tsan": ["-fsanitize=thread", "-fno-gpu-sanitize", "-g"]}  # (tsan: None where the toolchain cannot build it)
 
 
 @pytest.fixture(scope="module")

@@ -36,7 +36,7 @@ def test_group_kernel_body_equals_the_per_alignment_restatement(emulator, model_
 @pytest.fixture(scope="module")
 def emulator_tsan(tmp_path_factory):
     exe = os.path.join(str(tmp_path_factory.mktemp("model_emu_tsan")), "model_emu_tsan")
-    r = subprocess.run([CC, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-DRSEM_EMU", "-fsanitize=thread", "-Wno-unused-result", "-Wno-unused-value",
+    r = subprocess.run([CC, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-DRSEM_EMU", "-fsanitize=thread", "-fno-gpu-sanitize", "-Wno-unused-result", "-Wno-unused-value",
                         os.path.join(ROOT, "tests", "model_emu.cpp"), "-o", exe, "-lpthread"], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
     if r.returncode != 0:
         pytest.skip("no ThreadSanitizer build with this toolchain: " + r.stderr[-300:])
