@@ -126,7 +126,15 @@ int rsem_em_get_values(rsem_em_ctx* ctx, double* conprb, double* ncp);
  *                       alignments, a live model context).  0: bring them back now. */
 int rsem_em_set_option(rsem_em_ctx* ctx, const char* key, int64_t value);
 /* Layout facts: "value_bits", "value_range_bits", "reads_q32", "reads_sliced", "reads_long", "value_plane_bytes",
- * "sid_plane_bytes", "slots", "units", "csr_released" (0 / 1), "csr_bytes" (what "release_csr" frees). */
+ * "sid_plane_bytes", "slots", "units", "csr_released" (0 / 1), "csr_bytes" (what "release_csr" frees).
+ * How the E step deals the units of the sliced layout to its launches, in their order:
+ *   "units_compact"      units [0, units_compact) take no far-queue launch: the compact units, or all main units where the far
+ *                        queue is not used;
+ *   "units_main"         units [units_compact, units_main) take the far-queue launch; [units_main, units) are split rows;
+ *   "units_queued"       main units that qualify for the far-queue launch (a few ids outside their window per slice), whether or
+ *                        not it is taken (it is where they are at least one main unit in 25 and the far queue is on);
+ *   "unit_tables_agree"  1 if the device copy of the unit table holds the same units in the same order as the host copy, else 0
+ *                        (a diagnostic: it reads the table back). */
 int rsem_em_get_info(const rsem_em_ctx* ctx, const char* key, int64_t* value);
 /* Tuning aid (not part of the reference's surface): one E-step launch of the LANE kernel with per-workgroup start/end
  * timestamps (100 MHz clock), out[2u], out[2u+1] in dispatch order; *n_units_io = capacity in, units written out. */

@@ -970,6 +970,7 @@ struct rsem_em_ctx {
     // n_units_main): they are launched with the far-queue instantiation (k_estep_lane<.., kFQ = true>), beside the compact units on
     // stream_x.  far_queue = 0 (option / RSEM_HIP_FAR_QUEUE=0): one launch over all of them as until round 5.
     uint32_t n_units_compact = 0;
+    uint32_t n_units_queued = 0;  // main units that qualify for the far-queue launch, whether or not it is taken (partition_units)
     int far_queue = 1;
     hipStream_t stream_x = nullptr;
     hipEvent_t ev_x_fork = nullptr, ev_x_join = nullptr;
@@ -1016,6 +1017,12 @@ int resolved_kernel(const rsem_em_ctx* c) {
     return c->kernel == RSEM_EM_KERNEL_AUTO ? RSEM_EM_KERNEL_LANE : c->kernel;
 }
 
+// (field by field: a copy of a Unit need not keep the 4 padding bytes in front of its Shape)
+bool same_unit(const Unit& a, const Unit& b) {
+    return a.shape == b.shape && a.slice_begin == b.slice_begin && a.n_slices == b.n_slices && a.per_wave == b.per_wave && a.base == b.base &&
+           a.span == b.span && a.pad[0] == b.pad[0] && a.pad[1] == b.pad[1] && !memcmp(&a.S, &b.S, sizeof(Shape));
+}
+
 // the units of the split rows' shapes behind all the others (both parts keep their order), host and device copy
 int partition_units(rsem_em_ctx* c) {
     auto is_main = [](const Unit& u) { return u.S.fmt != kFmtF64X; };
@@ -1027,12 +1034,14 @@ int partition_units(rsem_em_ctx* c) {
     // against 0.650 ms, profiles/r06g_xrows_probe.log) -- and only where such units are worth a launch of their own (one unit in
     // twenty-five; configs[2] itself has 53 among 3 903 and paid 1 % for the second stream).
     auto queued = [](const Unit& u) { return u.pad[0] != 0 && (uint64_t)u.pad[1] <= 48ull * u.n_slices; };
-    const auto midc = std::stable_partition(c->h_units.begin(), mid, [&](const Unit& u) { return !queued(u); });
-    const uint32_t n_first = (uint32_t)(midc - c->h_units.begin());
-    c->n_units_compact = (c->far_queue && (c->n_units_main - n_first) * 25ull >= c->n_units_main) ? n_first : c->n_units_main;
-    if (c->n_units_compact != c->n_units_main && c->n_units)
-        RSEM_HIP_TRY(hipMemcpyAsync(c->d_units, c->h_units.data(), sizeof(Unit) * c->n_units, hipMemcpyHostToDevice, c->stream));
-    if (c->n_units_main != c->n_units && c->n_units)
+    c->n_units_queued = (uint32_t)std::count_if(c->h_units.begin(), mid, queued);
+    c->n_units_compact = c->n_units_main;
+    // (moved behind the others only where they get that launch: otherwise every unit keeps its place in the longest-first order)
+    if (c->far_queue && c->n_units_queued * 25ull >= c->n_units_main && c->n_units_queued)
+        c->n_units_compact = (uint32_t)(std::stable_partition(c->h_units.begin(), mid, [&](const Unit& u) { return !queued(u); }) - c->h_units.begin());
+    // the device copy follows every time, so that a unit's index means the same unit on both sides (tune_unit_order reads the
+    // trace in device order)
+    if (c->n_units)
         RSEM_HIP_TRY(hipMemcpyAsync(c->d_units, c->h_units.data(), sizeof(Unit) * c->n_units, hipMemcpyHostToDevice, c->stream));
     RSEM_HIP_TRY(hipStreamSynchronize(c->stream));
     return RSEM_OK;
@@ -1538,6 +1547,20 @@ int rsem_em_get_info(const rsem_em_ctx* c, const char* key, int64_t* value) {
     else if (!strcmp(key, "value_range_bits")) *value = c->value_range_bits;
     else if (!strcmp(key, "far_units")) *value = c->n_far_units;                        // units with an id outside their LDS window
     else if (!strcmp(key, "units")) *value = c->n_units;
+    else if (!strcmp(key, "units_compact")) *value = c->n_units_compact;              // [0, this): units launched without far queue
+    else if (!strcmp(key, "units_main")) *value = c->n_units_main;                    // [units_compact, this): far-queue launch; behind: split rows
+    else if (!strcmp(key, "units_queued")) *value = c->n_units_queued;                // main units fit for the far queue, adopted or not
+    else if (!strcmp(key, "unit_tables_agree")) {  // diagnostic: the device unit table holds the host one's units in the same order
+        std::vector<Unit> d(c->n_units);
+        if (c->n_units) {
+            RSEM_HIP_TRY(hipSetDevice(c->device));
+            RSEM_HIP_TRY(hipMemcpyAsync(d.data(), c->d_units, sizeof(Unit) * c->n_units, hipMemcpyDeviceToHost, c->stream));
+            RSEM_HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+        bool same = d.size() == c->h_units.size();
+        for (size_t i = 0; same && i < d.size(); i++) same = same_unit(d[i], c->h_units[i]);
+        *value = same ? 1 : 0;
+    }
     else if (!strcmp(key, "stray_reads")) *value = (int64_t)c->n_stray_reads;             // (a read with two stray ids counts twice)
     else if (!strcmp(key, "reads_q32")) *value = c->L.n_q32_rows;                       // reads held in Q32 planes
     else if (!strcmp(key, "reads_sliced")) *value = c->L.n_sell_rows;                   // reads in the sliced layout
@@ -1652,9 +1675,7 @@ static int tune_unit_order(rsem_em_ctx* c, const double* d_theta) {
         std::vector<Unit> sorted(n);
         for (uint32_t i = 0; i < n; i++) sorted[i] = c->h_units[order[i]];
         c->h_units.swap(sorted);
-        RSEM_HIP_TRY(hipMemcpyAsync(c->d_units, c->h_units.data(), sizeof(Unit) * n, hipMemcpyHostToDevice, c->stream));
-        RSEM_HIP_TRY(hipStreamSynchronize(c->stream));
-        rc = partition_units(c);
+        rc = partition_units(c);  // (uploads the new order)
         if (rc != RSEM_OK) return rc;
     }
     return RSEM_OK;
@@ -1831,8 +1852,9 @@ int rsem_em_run(rsem_em_ctx* c, double* theta, double N0, int round0, int min_ro
             if (r - round0 >= 3) RSEM_HIP_TRY(hipStreamWaitEvent(st, c->ev_s[(r - 2) & 3], 0));  // dst was cleared by round r-2's statistics
             if (prof && ti < timed) RSEM_HIP_TRY(hipEventRecord(c->events[2 + 2 * ti], st));
             {
+                // (as in the one-launch loop: with no compact unit at all, one launch of all units, their far ids inline)
                 const uint32_t nc = c->n_units_compact;
-                const bool far_launch = c->far_queue && nc < c->n_units;
+                const bool far_launch = c->far_queue && nc < c->n_units && nc > 0 && c->stream_x;
                 hipLaunchKernelGGL((k_estep_lane<true, false>), dim3(far_launch ? nc : c->n_units), dim3(kBlock), 0, st, c->L.d_shapes, c->d_units, c->L.T, c->M,
                                    (const double*)src, (const double*)(src + c->M + 1), N0, (const unsigned char*)c->d_sval, (const int16_t*)c->d_sexp, c->L.d_ssid, c->d_sncp, c->L.d_masks, dst,
                                    c->d_noise_a, dst + c->M + 1, (const Ctrl*)c->d_ctrl, (unsigned long long*)nullptr, SoloArgs());
