@@ -99,6 +99,9 @@ constexpr int kGroupBlk = 512;
 #define RSEM_GROUP_CHUNK 256
 #endif
 constexpr int kGroupChunk = RSEM_GROUP_CHUNK;  // rows per chunk (a multiple of the 32 rows a workgroup takes per step)
+// (a workgroup's last step in a chunk is not cut at the chunk's end: with any other value the rows behind it are counted twice)
+static_assert(kGroupBlk / 64 * 4 == 32 && (kGroupChunk == 0 || (kGroupChunk > 0 && kGroupChunk % 32 == 0)),
+              "RSEM_GROUP_CHUNK: 0 or a multiple of the 32 rows a workgroup takes per step");
 // 4 waves per SIMD (<= 128 VGPRs, a few dwords of scratch in the variants with the update) instead of the 2-3 the
 // allocator would settle for: 14.1 against 17.1 ms per round at a fifth of configs[2] (profiles/r04b_call.log) -- the kernel
 // waits on dependent loads, and the fourth wave hides more of them than the spills cost.
