@@ -525,6 +525,8 @@ __global__ __launch_bounds__(kBlock) void k_estep_lane(
         S.lg = G.lg;
         S.fmt = G.fmt;
         S.val_base = G.val_base;
+        S.cut = G.cut;
+        S.reserved = 0;
         const uint32_t u_end = S.slice_base + U.slice_begin + U.n_slices;
         const uint32_t s_begin = S.slice_base + U.slice_begin + (uint32_t)w * U.per_wave;
         const uint32_t s_end = min(u_end, s_begin + U.per_wave);
@@ -947,6 +949,8 @@ struct rsem_em_ctx {
     int* d_fill_err = nullptr;
     int value_bits = 64;              // 64: every read F64; 32: Q32 where a read qualifies
     int value_range_bits = 8;         // a read qualifies when its non-zero values span less than 2^this
+    int short_last_plane = 1;         // reads whose last value plane is a quarter or more empty take a short class (sell_shape.hpp: Shape::cut)
+    int short_min_units = kShortClassMinUnits;  // ... where the class fills this many units (short_classes_worth_it)
     bool layout_has_q32 = false;      // the current layout was built with Q32 shapes (from the then-current values)
     bool layout_ok = false;           // false between free_layout and a build_layout that went through (a failed rebuild)
     // LANE variant work list
@@ -1236,15 +1240,20 @@ int build_layout(rsem_em_ctx* c) {
     std::vector<Unit> units;
     // (not together with Q32 planes: which reads take that format is a documented function of their values alone)
     int split = c->split_rows && resolved_kernel(c) == RSEM_EM_KERNEL_LANE && !q32;
+    // (measurement knobs, applied to this build alone: the options keep what the caller set)
+    int short_on = c->short_last_plane, short_min_units = c->short_min_units;
+    if (const char* e = getenv("RSEM_HIP_SHORT_LAST_PLANE")) short_on = atoi(e) != 0;               // 0 = every plane full
+    if (const char* e = getenv("RSEM_HIP_SHORT_MIN_UNITS")) short_min_units = std::max(1, atoi(e));  // the class threshold
     if (const char* e = getenv("RSEM_HIP_SPLIT")) split = split && atoi(e) != 0;  // measurement knob: 0 = reads that leave their window stay whole
     // which reads split: those that are mostly outside their window (1), or every read with an id outside (2)
     if (split) split = c->split_policy;
     if (const char* e = getenv("RSEM_HIP_SPLIT_POLICY")) { if (split) split = !strcmp(e, "all") ? 2 : 1; }  // measurement knob
     int rc = sell_build_refined(c->L, c->stream, c->N1, c->M, c->d_row_ptr, c->d_sid, target_waves, c->forced_T,
-                                q32 ? c->d_cp : nullptr, c->value_range_bits, kWindow, units, &c->d_units, &c->n_stray_reads, split);
+                                q32 ? c->d_cp : nullptr, c->value_range_bits, kWindow, units, &c->d_units, &c->n_stray_reads, split,
+                                short_on ? short_min_units : 0);
     if (rc != RSEM_OK) return rc;
     if (c->L.n_x_rows) {
-        const size_t nxs = (size_t)(c->L.n_slots - c->L.x_slot_base);
+        const size_t nxs = (size_t)c->L.n_x_slots;
         RSEM_HIP_TRY(dmalloc(&c->d_xextra, nxs));
         RSEM_HIP_TRY(dmalloc(&c->d_xinv, nxs));
         RSEM_HIP_TRY(hipMemsetAsync(c->d_xextra, 0, sizeof(double) * std::max<size_t>(nxs, 1), c->stream));
@@ -1530,6 +1539,25 @@ int rsem_em_set_option(rsem_em_ctx* c, const char* key, int64_t value) {
         set_grid_for_kernel(c);
         return RSEM_OK;
     }
+    if (!strcmp(key, "short_last_plane") || !strcmp(key, "short_class_min_units")) {
+        // 1 (default): reads whose last value plane is at least a quarter empty are sorted into short classes whose last plane is
+        // stored compacted (sell_shape.hpp); 0: every plane holds 64 entries.  short_class_min_units: how many units a class must
+        // fill to be taken (a measurement knob; default kShortClassMinUnits).  Either rebuilds the layout.
+        const bool sw = !strcmp(key, "short_last_plane");
+        if (sw) RSEM_REQUIRE(value == 0 || value == 1, "short_last_plane must be 0 or 1");
+        else RSEM_REQUIRE(value >= 1 && value <= 1000000, "short_class_min_units must be in 1..1000000");
+        int& field = sw ? c->short_last_plane : c->short_min_units;
+        if (field == (int)value) return RSEM_OK;
+        field = (int)value;
+        if (!sw && !c->short_last_plane) return RSEM_OK;  // nothing built depends on it
+        RSEM_HIP_TRY(hipSetDevice(c->device));
+        { int rc0 = ensure_csr(c); if (rc0 != RSEM_OK) return rc0; }
+        free_layout(c);
+        int rc = build_layout(c);
+        if (rc != RSEM_OK) return rc;
+        set_grid_for_kernel(c);
+        return RSEM_OK;
+    }
     if (!strcmp(key, "check_every")) {
         RSEM_REQUIRE(value >= 1 && value <= kHistCap / 4, "check_every out of range");
         c->check_every = (int)value;
@@ -1566,6 +1594,12 @@ int rsem_em_get_info(const rsem_em_ctx* c, const char* key, int64_t* value) {
     else if (!strcmp(key, "reads_sliced")) *value = c->L.n_sell_rows;                   // reads in the sliced layout
     else if (!strcmp(key, "reads_long")) *value = c->L.n_long_rows;                     // reads left in the CSR
     else if (!strcmp(key, "value_plane_bytes")) *value = (int64_t)c->L.val_bytes;       // incl. padding
+    else if (!strcmp(key, "value_plane_entries")) *value = (int64_t)c->L.n_val_entries;  // incl. padding: / alignments in the layout = entries per alignment
+    else if (!strcmp(key, "short_last_plane")) *value = c->short_last_plane;
+    else if (!strcmp(key, "short_class_min_units")) *value = c->short_min_units;
+    else if (!strcmp(key, "short_classes")) *value = (int64_t)__builtin_popcountll(c->L.short_classes);  // classes that passed the threshold
+    else if (!strcmp(key, "shapes")) *value = c->L.n_shapes;
+    else if (!strcmp(key, "unit_bytes")) *value = (int64_t)sizeof(Unit);                 // one record of the unit table (a part of physical_bytes_per_launch)
     else if (!strcmp(key, "sid_plane_bytes")) *value = (int64_t)(c->L.n_planes * 256);
     else if (!strcmp(key, "slots")) *value = c->L.n_slots;
     else if (!strcmp(key, "sid_plane_bytes_loaded")) *value = (int64_t)(c->L.n_sid_planes_loaded * 256);  // slices where a tuple starts

@@ -177,10 +177,18 @@ RSEM_DEVFN void estep_block(const Shape& S, uint32_t s_begin, uint32_t s_end, in
     // offset -- no per-lane 64-bit address arithmetic.  The sids of a slice are loaded by all lanes or (mask 0, a scalar
     // branch) by none: lanes that do not start a tuple ignore theirs.
     const unsigned ulane = (unsigned)lane, uslot = ulane >> lg;
+    // The last value plane of a short class (sell_shape.hpp: Shape::cut) holds Gk < G entries per read, side by side: the lane's
+    // offset into it and the slice stride are other numbers, fixed for the whole block; a lane without an entry there loads its
+    // read's last one again (no predicate, no branch: see issue) and reduce() takes zero instead.  cut = 0: last_lane = lane,
+    // last_ok everywhere, the stride K * 64 -- the full layout.
+    const unsigned Gk = (unsigned)shape_Gk(S);
+    const unsigned last_lane = uslot * Gk + ((unsigned)g < Gk ? (unsigned)g : Gk - 1u);
+    const bool last_ok = (unsigned)g < Gk;
+    const uint32_t vstride = (uint32_t)RSEM_READFIRSTLANE((int)shape_val_stride(S));  // entries per slice, a scalar
     auto issue = [&](uint32_t t, unsigned long long m, SliceRegs<K, kQ>& b) {
         const uint32_t sl = t - S.slice_base;
-        const uint64_t v0 = (uint64_t)sl * (K * 64);              // first entry of the slice within the shape's planes
-        const ValT* __restrict__ vp = scp + v0;
+        const uint64_t v0 = (uint64_t)sl * (K * 64);              // first entry of the slice within the shape's sid planes
+        const ValT* __restrict__ vp = scp + (uint64_t)sl * vstride;  // ... and within its value planes
         // The sid planes of a slice are read only where a tuple starts in it (m != 0), then by all lanes: one scalar branch.
         // (Behind a branch the compiler counts the loads in flight as on the path with the fewest, so its wait for this
         // slice's planes also waits for the next slice's sid planes where that slice has them.  Issuing the same K loads
@@ -194,7 +202,8 @@ RSEM_DEVFN void estep_block(const Shape& S, uint32_t s_begin, uint32_t s_end, in
             for (int k = 0; k < K; k++) b.id[k] = ip[k * 64 + ulane];
         }
 #pragma unroll
-        for (int k = 0; k < K; k++) b.c[k] = stream_load(&vp[k * 64 + ulane]);
+        for (int k = 0; k < K - 1; k++) b.c[k] = stream_load(&vp[k * 64 + ulane]);
+        b.c[K - 1] = stream_load(&vp[(K - 1) * 64 + last_lane]);
         const uint32_t slot0 = S.slot_base + sl * R;
         // (all lanes of a read load its noise probability and exponent, not only the first: a load under a lane predicate
         // is a branch to the compiler, and with a conditional load in flight its waits for the OTHER loads turn into
@@ -304,7 +313,8 @@ RSEM_DEVFN void estep_block(const Shape& S, uint32_t s_begin, uint32_t s_end, in
 #pragma unroll
         for (int k = 0; k < K; k++) {
             // Q32: mantissa * 2^e is exact, so this is the F64 expression on the rounded value
-            const double cv = kQ ? (double)cur.c[k] * scale : (double)cur.c[k];
+            const ValT cr = (k == K - 1 && !last_ok) ? ValT(0) : cur.c[k];  // (a lane without an entry in a short last plane)
+            const double cv = kQ ? (double)cr * scale : (double)cr;
             double v = rth[k] * cv;
             if (v < kEpsilon) v = 0.0;
             f[k] = v;

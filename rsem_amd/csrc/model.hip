@@ -298,6 +298,10 @@ int launch_group_any(rsem_model_ctx* c, const double* d_theta, const AccumPtrs* 
         const int vrc = rsem::em_planes_view(c->em, &pv);
         if (vrc != RSEM_OK) return vrc;
     }
+    if (in_place && pv.n_shapes > kPlaneShapesMax) {  // (cannot happen: kMaxShapes == kShapeTableMax; the kernel's LDS copy holds no more)
+        rsem::set_last_error("the EM layout has %d shapes, the model kernel's table holds %d", pv.n_shapes, kPlaneShapesMax);
+        return RSEM_ERR_STATE;
+    }
     if (in_place) PO = PlaneOut{pv.d_rank, (const Shape*)pv.d_shapes, pv.n_shapes, pv.T, pv.n_sell_rows, pv.d_sval, pv.d_sncp};
     int rc;
     switch (c->D.model_type) {

@@ -109,7 +109,7 @@ struct PlaneOut {
     unsigned char* sval;
     double* sncp;
 };
-constexpr int kPlaneShapesMax = 96;  // >= kMaxShapes of sell_layout.hpp
+constexpr int kPlaneShapesMax = kShapeTableMax;  // every shape a layout can hold (sell_shape.hpp; sell_layout.hpp checks kMaxShapes against it)
 
 // the shape a sorted row belongs to: the last one whose first row is <= ps (binary search over the LDS copy)
 RSEM_DEVFN int plane_shape_of(const Shape* shapes, int n_shapes, uint32_t ps) {
@@ -458,10 +458,11 @@ RSEM_DEVFN void model_group_rows(const DevData& D, const DevTables& T, const dou
             W[m].len = active ? rl_v[m] : 0;
         }
         const int len1 = W[0].len, len2 = kPE ? W[kMates - 1].len : 0;
-        // the read's place in the sliced layout: alignment c goes to plane c >> lg of its slice, lane r * G + (c & (G - 1))
+        // the read's place in the sliced layout: alignment c goes to plane c >> lg of its slice, lane r * G + (c & (G - 1)) -- in
+        // the last plane of a short class the reads stand closer together: shape_val_off (sell_shape.hpp)
         double* plane = nullptr;
         double* nslot = nullptr;  // the read's noise value in the layout
-        int p_lg = 0;
+        int p_lg = 0, p_K = 1, p_cut = 0;
         uint32_t p_r = 0;
         if (PO.rank && valid) {
             const uint32_t ps = rank_v;
@@ -469,14 +470,15 @@ RSEM_DEVFN void model_group_rows(const DevData& D, const DevTables& T, const dou
                 const Shape& S = PO.shapes[plane_shape_of(PO.shapes, PO.n_shapes, ps)];
                 uint32_t slice_local;
                 row_to_slot(S, PO.T, ps - S.row_base, slice_local, p_r);
-                plane = (double*)(PO.sval + S.val_base) + (uint64_t)slice_local * S.K * 64;
+                plane = (double*)(PO.sval + S.val_base) + (uint64_t)slice_local * shape_val_stride(S);
                 nslot = PO.sncp + (S.slot_base + slice_local * shape_R(S) + p_r);
                 p_lg = S.lg;
-                p_r = (p_r << p_lg);  // first lane of the read within a plane row
+                p_K = S.K;
+                p_cut = S.cut;
             }
         }
         auto plane_put = [&](int c_idx, double v) {
-            if (plane) plane[(uint64_t)(c_idx >> p_lg) * 64 + p_r + (uint32_t)(c_idx & ((1 << p_lg) - 1))] = v;
+            if (plane) plane[shape_val_off(p_lg, p_K, p_cut, p_r, c_idx)] = v;
         };
 
         // per-chunk state carried from one chunk of a long read to the next: the window and product of the run that was open

@@ -33,8 +33,14 @@ namespace {
 #include "sell_shape.hpp"
 
 constexpr int kShapesPerFmt = 28;   // (lg 0..6) x (K 1..4)
-constexpr int kShapeBits = 7;
-constexpr int kMaxShapes = 3 * kShapesPerFmt;  // F64 shapes, then Q32 shapes, then F64X shapes (split rows)
+constexpr int kShapeBits = 8;
+// ids 0 .. 83: format * 28 + lg * 4 + K - 1 -- F64 shapes, then Q32 shapes, then F64X shapes (split rows) --, last plane full.
+// ids 84 .. 147: the SHORT CLASSES (sell_shape.hpp: Shape::cut) of F64, then of Q32: reads of lg >= 1 (K = 3 or 4) whose last
+// plane fills only q of the 4 quarters of their lane group: per format 2 (K) x [lg = 1: q = 2; lg = 2 .. 6: q = 1, 2, 3].
+constexpr int kFullShapes = 3 * kShapesPerFmt;
+constexpr int kShortPerFmt = 32;
+constexpr int kMaxShapes = kFullShapes + 2 * kShortPerFmt;
+static_assert(kMaxShapes <= kShapeTableMax, "the kernels that keep the shape table in LDS size it by kShapeTableMax (sell_shape.hpp)");
 constexpr int kShapeIds = 1 << kShapeBits;
 constexpr int kLongShape = kShapeIds - 1;      // rows with more than 256 alignments: CSR kernel
 constexpr uint32_t kKeyMinSidCap = (1u << (31 - kShapeBits)) - 1;  // sort key: shape | apart bit | anchor sid (capped) | hash of the tuple
@@ -54,19 +60,84 @@ __host__ __device__ inline bool q32_scale_of(double mx, double mn_nonzero, int r
     if (q.e < -1000 || q.e > 900) return false;
     return mn_nonzero >= ldexp(mx, -range_bits);
 }
+// ... and the scan of a read's values that feeds it: the ONE statement of "does this read take Q32" (row_key_of folds the scan
+// into its own pass over the read; k_row_length_hist and the emulators call row_takes_q32)
+struct Q32Range {
+    double vmx = 0.0, vmn = 1.79e308;
+    __host__ __device__ void add(double v) {
+        if (!(v >= 0.0)) vmx = 1e308;  // negative / NaN: never compressed
+        vmx = fmax(vmx, v);
+        if (v > 0.0) vmn = fmin(vmn, v);
+    }
+    __host__ __device__ bool takes_q32(int range_bits, Q32Scale& q) const { return q32_scale_of(vmx, vmn, range_bits, q); }
+};
+__host__ __device__ inline bool row_takes_q32(const double* __restrict__ cp, uint64_t fr, uint64_t to, int range_bits) {
+    Q32Range r;
+    for (uint64_t j = fr; j < to; j++) r.add(cp[j]);
+    Q32Scale q;
+    return r.takes_q32(range_bits, q);
+}
 __host__ __device__ inline uint32_t q32_mantissa(double v, int e) {
     const double m = rint(ldexp(v, -e));      // exact scaling, round to nearest even
     return m >= 4294967295.0 ? 0xffffffffu : (uint32_t)m;
 }
 
-__host__ __device__ inline int shape_id_of(uint64_t L) {
+// short class (lg 1..6, K 3..4, q quarters used) -> 0 .. 31; -1: there is no such class
+__host__ __device__ inline int short_class_index(int lg, int K, int q) {
+    if (lg < 1 || lg > 6 || K < 3 || K > 4 || q < 1 || q > 3) return -1;
+    if (lg == 1) return q == 2 ? (K - 3) : -1;
+    return 2 + (lg - 2) * 6 + (K - 3) * 3 + (q - 1);
+}
+// The one table from a shape id to what it means.  false: not a shape of the sliced layout.
+__host__ __device__ inline bool shape_of_id(int id, int& fmt, int& lg, int& K, int& cut) {
+    if (id < 0 || id >= kMaxShapes) return false;
+    if (id < kFullShapes) {
+        fmt = id / kShapesPerFmt;
+        lg = (id % kShapesPerFmt) / 4;
+        K = id % 4 + 1;
+        cut = 0;
+        return true;
+    }
+    const int j = id - kFullShapes, i = j % kShortPerFmt;
+    fmt = j / kShortPerFmt;  // kFmtF64 / kFmtQ32
+    if (i < 2) { lg = 1; K = 3 + i; cut = 2; return true; }
+    lg = 2 + (i - 2) / 6;
+    K = 3 + ((i - 2) % 6) / 3;
+    cut = 3 - (i - 2) % 3;  // q = 1, 2, 3
+    return true;
+}
+__host__ __device__ inline int shape_fmt_of_id(int id) { return id < kFullShapes ? id / kShapesPerFmt : (id - kFullShapes) / kShortPerFmt; }
+// the full shape a short class folds back to (same format, lg, K)
+__host__ __device__ inline int full_shape_of_id(int id) {
+    int fmt, lg, K, cut;
+    if (id < kFullShapes || !shape_of_id(id, fmt, lg, K, cut)) return id;
+    return fmt * kShapesPerFmt + lg * 4 + K - 1;
+}
+
+// The shape of a read of L alignments, as an id of the F64 format (row_key_of moves it to the Q32 / F64X twin).
+// short_classes: bit i set = reads of short class i take its shape (kFullShapes + i); 0 (default): every read takes the full
+// shape of its (lg, K), the layout of the Gibbs contexts and of everything built before the classes existed.
+// even_quarters (the Q32 format): q is rounded up to 2 or 4, so that a slice of 4-byte entries keeps a stride of whole 128-byte
+// lines (256 K - 64 * cut bytes) and every shape behind it starts on one; Q32 therefore uses the q = 2 classes only.
+__host__ __device__ inline int shape_id_of(uint64_t L, uint32_t short_classes = 0, bool even_quarters = false) {
     if (L <= 4) return (int)(L == 0 ? 0 : L - 1);  // lg = 0, K = L
     int lg = 1;
     uint64_t cap = 8;
     while (L > cap) { cap <<= 1; ++lg; }
     if (lg > 6) return kLongShape;
     int K = (int)((L + (1u << lg) - 1) >> lg);  // 3 or 4
+    if (short_classes) {
+        const int G = 1 << lg, n_last = (int)L - (K - 1) * G;  // 1 .. G entries in the last plane
+        int q = (n_last * 4 + G - 1) >> lg;                    // quarters of the lane group they reach into
+        if (even_quarters) q = (q + 1) & ~1;
+        const int i = short_class_index(lg, K, q);
+        if (i >= 0 && ((short_classes >> i) & 1u)) return kFullShapes + i;
+    }
     return lg * 4 + (K - 1);
+}
+// ... moved to format fmt (kFmtQ32 / kFmtF64X; split rows have no short classes: callers give them full shapes)
+__host__ __device__ inline int shape_id_in_fmt(int id, int fmt) {
+    return id < kFullShapes ? id + fmt * kShapesPerFmt : id + fmt * kShortPerFmt;
 }
 
 // ... and back: (slice within the shape, row slot within the slice) -> sorted read q of the shape.  false: the slot is empty
@@ -116,22 +187,18 @@ constexpr int kMedianExactMax = 64; // reads up to this length: exact median (ra
 // longer holds a foreign id.
 __host__ __device__ inline uint64_t row_key_of(uint64_t i, int32_t M, const uint64_t* __restrict__ row_ptr,
                                                const int32_t* __restrict__ sid, const double* __restrict__ cp, int range_bits,
-                                               int apart, int* err, int split = 0, uint32_t* split_far = nullptr) {
+                                               int apart, int* err, int split = 0, uint32_t* split_far = nullptr,
+                                               uint64_t short_classes = 0 /* bits 0..31: F64 classes, 32..63: Q32 classes */) {
     uint64_t fr = row_ptr[i], to = row_ptr[i + 1];
     if (to < fr) { *err = 1; return 0; }
     uint32_t h = 0x811c9dc5u, mn = 0xffffffffu;
-    double vmx = 0.0, vmn = 1.79e308;
+    Q32Range vr;
     for (uint64_t j = fr; j < to; j++) {
         int32_t s = sid[j];
         if (s < 1 || s > M) { *err = 2; s = 1; }
         h = mix32(h, (uint32_t)s);
         mn = (uint32_t)s < mn ? (uint32_t)s : mn;
-        if (cp) {
-            const double v = cp[j];
-            if (!(v >= 0.0)) vmx = 1e308;  // negative / NaN: never compressed
-            vmx = fmax(vmx, v);
-            if (v > 0.0) vmn = fmin(vmn, v);
-        }
+        if (cp) vr.add(cp[j]);
     }
     const uint64_t L = to - fr;
     if (L > 1 && !*err) {
@@ -164,7 +231,7 @@ __host__ __device__ inline uint64_t row_key_of(uint64_t i, int32_t M, const uint
             if (v < mn || v >= mn + (uint32_t)apart) far = 1;
             else { ++L_in; h_in = mix32(h_in, v); }
         }
-    int shape = shape_id_of(to - fr);
+    int shape = shape_id_of(to - fr);  // (the full shape: the class is chosen below, once the format is known)
     // Split only where the far alignments are at least half of the read (a read without a gene to speak of: each of its
     // alignments would otherwise be a global atomic per round).  A read of a gene that ALSO hits a few transcripts elsewhere
     // stays whole: as a row of its own shape its tuple runs are too short for the lane kernel to skip anything (a wave
@@ -172,32 +239,92 @@ __host__ __device__ inline uint64_t row_key_of(uint64_t i, int32_t M, const uint
     // (configs[2] with 10 % such reads: 1.48 ms split against 1.17-1.25 whole, profiles/r04d_call.log).
     // split == 2: every read with an id outside splits (the X units then run beside the compact ones: em.hip launch_estep)
     if (far && split && (split == 2 || 2 * L_in <= L) && shape != kLongShape && (uint64_t)mn <= kKeyMinSidCap) {  // split row: keyed by its in-window part
-        shape = shape_id_of(L_in) + 2 * kShapesPerFmt;
+        shape = shape_id_in_fmt(shape_id_of(L_in), kFmtF64X);
         if (split_far) *split_far = (uint32_t)(L - L_in);
         return ((uint64_t)shape << (64 - kShapeBits)) | ((uint64_t)mn << 32) | h_in;
     }
     if (mn > kKeyMinSidCap) mn = kKeyMinSidCap;
     Q32Scale q;
-    if (cp && shape != kLongShape && q32_scale_of(vmx, vmn, range_bits, q)) shape += kShapesPerFmt;
+    if (shape != kLongShape) {
+        const bool q32 = cp && vr.takes_q32(range_bits, q);
+        if (short_classes) shape = shape_id_of(to - fr, (uint32_t)(short_classes >> (q32 ? 32 : 0)), q32);
+        if (q32) shape = shape_id_in_fmt(shape, kFmtQ32);
+    }
     return ((uint64_t)shape << (64 - kShapeBits)) | (far << kKeyApartBit) | ((uint64_t)mn << 32) | h;
 }
 
 __global__ void k_row_keys(uint64_t N1, int32_t M, const uint64_t* __restrict__ row_ptr,
                            const int32_t* __restrict__ sid, const double* __restrict__ cp, int range_bits, int apart, int split,
                            const unsigned char* __restrict__ also_apart, uint64_t* keys, uint32_t* vals, int* err,
-                           unsigned long long* n_split = nullptr /* [0] rows that split, [1] their far alignments */) {
+                           unsigned long long* n_split = nullptr /* [0] rows that split, [1] their far alignments */, uint64_t short_classes = 0) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N1) return;
     int e = 0;
     uint32_t nf = 0;
-    uint64_t key = row_key_of(i, M, row_ptr, sid, cp, range_bits, apart, &e, split, &nf);
+    uint64_t key = row_key_of(i, M, row_ptr, sid, cp, range_bits, apart, &e, split, &nf, short_classes);
     if (n_split && nf) { atomicAdd(&n_split[0], 1ull); atomicAdd(&n_split[1], (unsigned long long)nf); }
     // (a read the first layout found outside its unit's window; split rows have no such bit: their key's hash is all 32 bits)
-    if (also_apart && also_apart[i] && (int)(key >> (64 - kShapeBits)) < 2 * kShapesPerFmt) key |= 1ull << kKeyApartBit;
+    if (also_apart && also_apart[i] && shape_fmt_of_id((int)(key >> (64 - kShapeBits))) != kFmtF64X) key |= 1ull << kKeyApartBit;
     if (e) *err = e;
     if (e == 1) return;
     keys[i] = key;
     vals[i] = (uint32_t)i;
+}
+
+// ---- which short classes are worth a shape of their own ---------------------------------------------------------------------
+// Rows per (format, length), lengths 0 .. 256: one pass over the row lengths (and, where reads may take the Q32 format, over
+// their values: the rule of row_key_of), before the keys are made.
+constexpr int kLenHist = 257;
+__global__ void k_row_length_hist(uint64_t N1, const uint64_t* __restrict__ row_ptr, const double* __restrict__ cp, int range_bits,
+                                  unsigned long long* hist /* [2 * kLenHist] */) {
+    __shared__ unsigned int h[2 * kLenHist];
+    for (int i = threadIdx.x; i < 2 * kLenHist; i += blockDim.x) h[i] = 0;
+    __syncthreads();
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N1; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t fr = row_ptr[i], to = row_ptr[i + 1];
+        if (to < fr || to - fr > 256) continue;
+        const int fmt = (cp && row_takes_q32(cp, fr, to, range_bits)) ? kFmtQ32 : kFmtF64;
+        atomicAdd(&h[fmt * kLenHist + (int)(to - fr)], 1u);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * kLenHist; i += blockDim.x)
+        if (h[i]) atomicAdd(&hist[i], (unsigned long long)h[i]);
+}
+// A short class takes 16 * cut entries off every slice of its reads -- and takes its reads out of the full shape of their
+// (lg, K), so that both are sorted by anchor on their own: each has fewer reads per transcript id, a unit of either (4 blocks
+// of T slices) spans more ids, and beyond one LDS window (kLayoutWindow ids) a unit's reads run the loop with the global
+// gather and atomics.  A class is enabled when its reads fill at least `min_units` units of 4 * T slices; the others keep the
+// full shape (bit clear).  hist: k_row_length_hist; T: an estimate of what sell_build will choose (slices summed per length
+// here, per shape there; reads that split or stay in the CSR are not known yet) -- the two differ by a few slices in millions.
+#ifndef RSEM_SHORT_CLASS_MIN_UNITS
+#define RSEM_SHORT_CLASS_MIN_UNITS 8
+#endif
+// The threshold: a class thinner than this is mostly partial tail units (sell_build_units cuts the end of every shape into
+// quarter-size units) and windows staged for a few reads each.  PROVISIONAL: 8 is reasoned, not measured -- the sweep over
+// configs[2] and its side legs is an open item in profiles/HISTORY.md (option "short_class_min_units" is there for it).
+constexpr int kShortClassMinUnits = RSEM_SHORT_CLASS_MIN_UNITS;
+inline uint64_t short_classes_worth_it(const unsigned long long* hist, uint32_t target_waves, uint32_t forced_T, int min_units) {
+    uint64_t rows[2][kShortPerFmt] = {}, n_slices = 0;
+    for (int f = 0; f < 2; f++)
+        for (int L = 1; L < kLenHist; L++) {
+            const unsigned long long n = hist[f * kLenHist + L];
+            if (!n) continue;
+            int fmt, lg, K, cut;
+            const int id = shape_id_of((uint64_t)L, 0xffffffffu, f == kFmtQ32);
+            shape_of_id(id, fmt, lg, K, cut);
+            n_slices += (n + (64u >> lg) - 1) >> (6 - lg);  // (an estimate: sell_build rounds up once per shape, not per length)
+            if (id >= kFullShapes) rows[f][id - kFullShapes] += n;
+        }
+    const uint32_t T = forced_T ? forced_T : std::min<uint64_t>(256, std::max<uint64_t>(8, n_slices / std::max(1u, target_waves)));
+    uint64_t mask = 0;
+    for (int f = 0; f < 2; f++)
+        for (int i = 0; i < kShortPerFmt; i++) {
+            int fmt, lg, K, cut;
+            shape_of_id(kFullShapes + i, fmt, lg, K, cut);
+            const uint64_t slices = rows[f][i] >> (6 - lg);
+            if (slices >= (uint64_t)min_units * 4 * T && slices > 0) mask |= 1ull << (f * 32 + i);
+        }
+    return mask;
 }
 
 __global__ void k_shape_bounds(uint64_t N1, const uint64_t* __restrict__ keys, uint32_t* first) {
@@ -232,7 +359,8 @@ __host__ __device__ inline void sell_fill_row(const Shape& S, uint32_t T, uint32
     uint32_t orig = order[p];
     uint64_t fr = row_ptr[orig];
     int L = (int)(row_ptr[orig + 1] - fr);
-    const uint64_t pl_local = (uint64_t)slice_local * S.K * 64;   // first entry of the slice, within the shape
+    const uint64_t pl_local = (uint64_t)slice_local * S.K * 64;   // first entry of the slice, within the shape's sid planes
+    const uint64_t vl_local = (uint64_t)slice_local * shape_val_stride(S);  // ... and within its value planes
     const uint64_t pl0 = S.plane_base * 64 + pl_local;
     const uint32_t slot = S.slot_base + slice_local * shape_R(S) + r;
     Q32Scale q{0};
@@ -247,11 +375,14 @@ __host__ __device__ inline void sell_fill_row(const Shape& S, uint32_t T, uint32
     for (int c = 0; c < L; c++) {
         if (S.fmt == kFmtF64X && !in_split_window(sid[fr + c], anchor, reach)) continue;
         const uint64_t off = (uint64_t)(ci >> S.lg) * 64 + r * G + (ci & (G - 1));
+        bool ok;
+        const uint64_t voff = vl_local + shape_val_off(S, r, ci, &ok);
         ++ci;
+        if (!ok) { if (err) *err = 4; continue; }  // (the read is longer than its shape: never written anywhere)
         if (kIds) ssid[pl0 + off] = sid[fr + c];
         if (cp) {
-            if (S.fmt == kFmtQ32) ((uint32_t*)(sval + S.val_base))[pl_local + off] = q32_mantissa(cp[fr + c], q.e);
-            else ((double*)(sval + S.val_base))[pl_local + off] = cp[fr + c];
+            if (S.fmt == kFmtQ32) ((uint32_t*)(sval + S.val_base))[voff] = q32_mantissa(cp[fr + c], q.e);
+            else ((double*)(sval + S.val_base))[voff] = cp[fr + c];
         }
     }
     if (ncp) sncp[slot] = ncp[orig];
@@ -259,12 +390,9 @@ __host__ __device__ inline void sell_fill_row(const Shape& S, uint32_t T, uint32
 
 // The inverse of sell_fill_row for F64 rows: the caller-order CSR (ids and values) of sorted row p, read back from the planes --
 // the same doubles, so a CSR that was released to save memory (rsem_em_set_option "release_csr") is restored bit for bit.
-__global__ void k_unfill_sell(const Shape* __restrict__ shapes, int n_shapes, uint32_t T, uint32_t n_sell_rows,
-                              const uint32_t* __restrict__ order, const uint64_t* __restrict__ row_ptr, const int32_t* __restrict__ ssid,
-                              const unsigned char* __restrict__ sval, int32_t* sid, double* cp) {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n_sell_rows) return;
-    const Shape S = shapes[find_shape_by_row(shapes, n_shapes, p)];
+__host__ __device__ inline void sell_unfill_row(const Shape& S, uint32_t T, uint32_t p, const uint32_t* __restrict__ order,
+                                                const uint64_t* __restrict__ row_ptr, const int32_t* __restrict__ ssid,
+                                                const unsigned char* __restrict__ sval, int32_t* sid, double* cp) {
     const int G = shape_G(S);
     uint32_t slice_local, r;
     row_to_slot(S, T, p - S.row_base, slice_local, r);
@@ -272,12 +400,20 @@ __global__ void k_unfill_sell(const Shape* __restrict__ shapes, int n_shapes, ui
     const uint64_t fr = row_ptr[orig];
     const int L = (int)(row_ptr[orig + 1] - fr);
     const uint64_t pl_local = (uint64_t)slice_local * S.K * 64;
+    const uint64_t vl_local = (uint64_t)slice_local * shape_val_stride(S);
     const uint64_t pl0 = S.plane_base * 64 + pl_local;
     for (int c = 0; c < L; c++) {
         const uint64_t off = (uint64_t)(c >> S.lg) * 64 + r * G + (c & (G - 1));
         sid[fr + c] = ssid[pl0 + off];
-        cp[fr + c] = ((const double*)(sval + S.val_base))[pl_local + off];
+        cp[fr + c] = ((const double*)(sval + S.val_base))[vl_local + shape_val_off(S, r, c)];
     }
+}
+__global__ void k_unfill_sell(const Shape* __restrict__ shapes, int n_shapes, uint32_t T, uint32_t n_sell_rows,
+                              const uint32_t* __restrict__ order, const uint64_t* __restrict__ row_ptr, const int32_t* __restrict__ ssid,
+                              const unsigned char* __restrict__ sval, int32_t* sid, double* cp) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_sell_rows) return;
+    sell_unfill_row(shapes[find_shape_by_row(shapes, n_shapes, p)], T, p, order, row_ptr, ssid, sval, sid, cp);
 }
 
 // d_xanchor: anchors of the split rows, indexed by sorted row - x_row_base (nullptr: no split rows)
@@ -495,6 +631,8 @@ struct SellLayout {
     uint32_t n_slots = 0;
     uint64_t n_planes = 0;
     uint64_t val_bytes = 0;       // value planes of all shapes (Shape::val_base points into them)
+    uint64_t n_val_entries = 0;   // entries of those planes (short classes: less than n_planes * 64)
+    uint64_t short_classes = 0;   // the short classes this layout was built with (row_key_of)
     uint32_t n_q32_rows = 0;      // sorted rows held in Q32 shapes
     uint64_t n_q32_planes = 0;
     uint64_t n_sid_planes_loaded = 0;  // sid planes of the slices in which some lane starts a new tuple (k_count_sid_planes)
@@ -504,7 +642,7 @@ struct SellLayout {
     uint64_t n_far = 0;                      // alignments of split rows outside their window
     uint32_t* d_xanchor = nullptr;           // [n_x_rows]
     uint32_t* d_xreach = nullptr;            // [n_x_rows] ids [anchor, anchor + reach) stay in the row (nullptr: kLayoutWindow for every row)
-    uint32_t n_x_slots = 0;                  // n_slots - x_slot_base
+    uint32_t n_x_slots = 0;                  // row slots of the split shapes
     uint64_t* d_far_ptr = nullptr;           // [n_x_slots + 1] far entries of the split row in slot x_slot_base + xs, in file order
     int32_t* d_far_sid = nullptr;            // [n_far]
     uint64_t* d_far_src = nullptr;           // [n_far] index into the caller's CSR
@@ -528,7 +666,7 @@ inline void sell_free(SellLayout& L) {
 }
 
 // (re)write the value planes / per-slot noise values (and exponents of the Q32 reads) from the caller-order arrays.
-// d_sval: L.val_bytes bytes (= n_planes * 512 for a layout without Q32 shapes); d_sexp / d_err only with Q32 shapes.
+// d_sval: L.val_bytes bytes (8 or 4 per entry of L.n_val_entries: n_planes * 512 for a layout of full F64 shapes); d_sexp / d_err only with Q32 shapes.
 inline int sell_fill_values(const SellLayout& L, hipStream_t st, const uint64_t* d_row_ptr, const double* d_cp,
                             const double* d_ncp, void* d_sval, double* d_sncp, int16_t* d_sexp = nullptr,
                             int* d_err = nullptr, const int32_t* d_sid = nullptr) {
@@ -557,8 +695,7 @@ inline int sell_fill_values(const SellLayout& L, hipStream_t st, const uint64_t*
 inline int sell_build_far(SellLayout& L, hipStream_t st, const uint64_t* d_row_ptr, const int32_t* d_sid, const uint64_t* d_keys_sorted) {
     const uint32_t nx = L.n_x_rows;
     if (!nx) return RSEM_OK;
-    const uint32_t nxs = L.n_slots - L.x_slot_base;
-    L.n_x_slots = nxs;
+    const uint32_t nxs = L.n_x_slots;
     if (d_keys_sorted) {
         RSEM_HIP_TRY(dmalloc(&L.d_xanchor, nx));
         hipLaunchKernelGGL(k_x_anchors, dim3(rsem::ceil_div(nx, kBlock)), dim3(kBlock), 0, st, nx, L.x_row_base, d_keys_sorted, L.d_xanchor);
@@ -635,7 +772,8 @@ inline int sell_build_far(SellLayout& L, hipStream_t st, const uint64_t* d_row_p
 // qualify (q32_scale_of with range_bits) are placed in Q32 shapes.
 inline int sell_build(SellLayout& L, hipStream_t st, uint64_t N1, int32_t M, const uint64_t* d_row_ptr,
                       const int32_t* d_sid, uint32_t target_waves, uint32_t forced_T = 0,
-                      const double* d_cp_for_q32 = nullptr, int range_bits = 0, const unsigned char* d_also_apart = nullptr, int split = 0) {
+                      const double* d_cp_for_q32 = nullptr, int range_bits = 0, const unsigned char* d_also_apart = nullptr, int split = 0,
+                      int short_min_units = 0 /* 0: no short classes; else the threshold of short_classes_worth_it */) {
     L.N1 = N1;
     int apart = kLayoutWindow;
     if (const char* e = getenv("RSEM_HIP_APART")) apart = atoi(e) ? kLayoutWindow : 0;  // measurement knob: 0 = one sorted sequence per shape
@@ -655,6 +793,24 @@ inline int sell_build(SellLayout& L, hipStream_t st, uint64_t N1, int32_t M, con
     RSEM_HIP_TRY(dmalloc(&d_err, 1));
     RSEM_HIP_TRY(hipMemsetAsync(d_err, 0, sizeof(int), st));
     RSEM_HIP_TRY(hipMemsetAsync(d_first, 0xff, kShapeIds * sizeof(uint32_t), st));
+    uint64_t short_classes = 0;
+    if (N1 && short_min_units > 0) {
+        unsigned long long* d_hist = nullptr;
+        unsigned long long h_hist[2 * kLenHist];
+        RSEM_HIP_TRY(dmalloc(&d_hist, 2 * kLenHist));
+        hipError_t e = hipMemsetAsync(d_hist, 0, sizeof(h_hist), st);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_row_length_hist, dim3((unsigned)std::min<uint64_t>(4096, rsem::ceil_div(N1, kBlock))), dim3(kBlock), 0, st, N1, d_row_ptr,
+                               d_cp_for_q32, range_bits, d_hist);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(h_hist, d_hist, sizeof(h_hist), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        (void)hipFree(d_hist);
+        if (e != hipSuccess) { cleanup(); RSEM_HIP_TRY(e); }
+        short_classes = short_classes_worth_it(h_hist, target_waves, forced_T, short_min_units);
+    }
+    L.short_classes = short_classes;
     if (N1) {
         // Split rows pay for two more passes and the kernel-sequence loop: taken only where they carry weight -- at least one
         // read in twenty would split (a read splits where most of its alignments lie outside its window: row_key_of).
@@ -665,7 +821,7 @@ inline int sell_build(SellLayout& L, hipStream_t st, uint64_t N1, int32_t M, con
             RSEM_HIP_TRY(dmalloc(&d_ns, 2));
             RSEM_HIP_TRY(hipMemsetAsync(d_ns, 0, 2 * sizeof(unsigned long long), st));
             hipLaunchKernelGGL(k_row_keys, dim3(rsem::ceil_div(N1, kBlock)), dim3(kBlock), 0, st, N1, M, d_row_ptr, d_sid,
-                               d_cp_for_q32, range_bits, apart, do_split, d_also_apart, d_keys, d_vals, d_err, d_ns);
+                               d_cp_for_q32, range_bits, apart, do_split, d_also_apart, d_keys, d_vals, d_err, d_ns, short_classes);
             RSEM_HIP_TRY(hipGetLastError());
             RSEM_HIP_TRY(hipMemcpyAsync(h_ns, d_ns, sizeof(h_ns), hipMemcpyDeviceToHost, st));
             RSEM_HIP_TRY(hipStreamSynchronize(st));
@@ -673,7 +829,7 @@ inline int sell_build(SellLayout& L, hipStream_t st, uint64_t N1, int32_t M, con
         }
         if (!do_split) {
             hipLaunchKernelGGL(k_row_keys, dim3(rsem::ceil_div(N1, kBlock)), dim3(kBlock), 0, st, N1, M, d_row_ptr, d_sid,
-                               d_cp_for_q32, range_bits, apart, 0, d_also_apart, d_keys, d_vals, d_err, (unsigned long long*)nullptr);
+                               d_cp_for_q32, range_bits, apart, 0, d_also_apart, d_keys, d_vals, d_err, (unsigned long long*)nullptr, short_classes);
             RSEM_HIP_TRY(hipGetLastError());
         }
         size_t tb = 0;
@@ -705,6 +861,7 @@ inline int sell_build(SellLayout& L, hipStream_t st, uint64_t N1, int32_t M, con
     L.x_slot_base = 0;
     L.n_far = 0;
     L.n_x_slots = 0;
+    L.n_val_entries = 0;
     uint32_t long_first = (h_first[kLongShape] == 0xffffffffu) ? (uint32_t)N1 : h_first[kLongShape];
     L.n_sell_rows = long_first;
     L.n_long_rows = (uint32_t)N1 - long_first;
@@ -714,9 +871,11 @@ inline int sell_build(SellLayout& L, hipStream_t st, uint64_t N1, int32_t M, con
         for (int j = id + 1; j < kMaxShapes; j++)
             if (h_first[j] != 0xffffffffu) { next = h_first[j]; break; }
         Shape& S = L.h_shapes[L.n_shapes++];
-        S.fmt = id / kShapesPerFmt;
-        S.lg = (id % kShapesPerFmt) / 4;
-        S.K = id % 4 + 1;
+        {
+            int fmt = 0, lg = 0, K = 1, cut = 0;
+            shape_of_id(id, fmt, lg, K, cut);
+            S.fmt = fmt; S.lg = lg; S.K = K; S.cut = cut; S.reserved = 0;
+        }
         S.row_base = h_first[id];
         S.n_rows = next - h_first[id];
         uint32_t rps = shape_R(S);
@@ -728,11 +887,13 @@ inline int sell_build(SellLayout& L, hipStream_t st, uint64_t N1, int32_t M, con
         L.n_slices += S.n_slices;
         L.n_planes += (uint64_t)S.n_slices * S.K;
         L.n_slots += S.n_slices * rps;
-        L.val_bytes += (uint64_t)S.n_slices * S.K * plane_bytes(S.fmt);
+        L.val_bytes += shape_val_bytes(S);
+        L.n_val_entries += (uint64_t)S.n_slices * shape_val_stride(S);
         if (S.fmt == kFmtQ32) { L.n_q32_rows += S.n_rows; L.n_q32_planes += (uint64_t)S.n_slices * S.K; }
-        if (S.fmt == kFmtF64X) {  // (the split shapes are the last ones of the table: their rows and slots are contiguous)
+        if (S.fmt == kFmtF64X) {  // (the split shapes follow each other in the table: their rows and slots are contiguous)
             if (!L.n_x_rows) { L.x_row_base = S.row_base; L.x_slot_base = S.slot_base; }
             L.n_x_rows += S.n_rows;
+            L.n_x_slots += S.n_slices * rps;
         }
     }
     // slices per block: enough blocks to fill the chip a few times over, long enough lane runs
@@ -989,7 +1150,7 @@ __global__ __launch_bounds__(256) void k_mark_stray_reads(const Unit* __restrict
         if (!slot_to_row(S, T, sl, r, q)) continue;  // (cannot happen: an empty slot holds id 0)
         const uint32_t orig = order[S.row_base + q];
         int e = 0;
-        const uint64_t key = row_key_of(orig, M, row_ptr, sid, nullptr, 0, kLayoutWindow, &e);
+        const uint64_t key = row_key_of(orig, M, row_ptr, sid, nullptr, 0, kLayoutWindow, &e);  // (only its apart bit is used: the shape does not matter)
         if (((key >> kKeyApartBit) & 1ull) == 0ull && also_apart[orig] == 0) {  // (a far-reaching read is where it belongs already)
             also_apart[orig] = 1;
             ++mine;
@@ -1002,14 +1163,15 @@ __global__ __launch_bounds__(256) void k_mark_stray_reads(const Unit* __restrict
 // `units` (allocated here; the caller owns it).  RSEM_HIP_APART=0 switches the apart bit and this refinement off.
 inline int sell_build_refined(SellLayout& L, hipStream_t st, uint64_t N1, int32_t M, const uint64_t* d_row_ptr, const int32_t* d_sid,
                               uint32_t target_waves, uint32_t forced_T, const double* d_cp_for_q32, int range_bits, int window_cap,
-                              std::vector<Unit>& units, Unit** d_units, unsigned long long* n_strays = nullptr, int split = 0) {
+                              std::vector<Unit>& units, Unit** d_units, unsigned long long* n_strays = nullptr, int split = 0,
+                              int short_min_units = 0) {
     unsigned char* d_also = nullptr;
     unsigned long long* d_n = nullptr;
     if (n_strays) *n_strays = 0;
     const char* knob = getenv("RSEM_HIP_APART");
     const bool refine = !(knob && atoi(knob) == 0);
     for (int pass = 0; pass < 2; pass++) {
-        int rc = sell_build(L, st, N1, M, d_row_ptr, d_sid, target_waves, forced_T, d_cp_for_q32, range_bits, d_also, split);
+        int rc = sell_build(L, st, N1, M, d_row_ptr, d_sid, target_waves, forced_T, d_cp_for_q32, range_bits, d_also, split, short_min_units);
         if (rc == RSEM_OK) rc = sell_build_units(L, units, window_cap);
         if (rc != RSEM_OK) { (void)hipFree(d_also); return rc; }
         (void)hipFree(*d_units);
