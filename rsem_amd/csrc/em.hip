@@ -14,7 +14,7 @@
 //     read l / G.  Every global load of the hot loop is therefore a fully coalesced 256 B (sid) or
 //     512 B (conprb) wave access, whatever the row length (1..256 alignments per read).
 //   * per-read normaliser: xor-shuffle reduction over the G lanes of a read;
-//   * per-transcript counts (LANE kernel, the default): inside a block of slices a lane follows consecutive
+//   * per-transcript counts (k_estep_lane): inside a block of slices a lane follows consecutive
 //     sorted reads; while their sid tuple does not change it keeps the partial counts in registers and
 //     skips the sid planes; on a change it spills into a 2048-entry LDS count window, which leaves the
 //     workgroup as one device atomic per touched sid;
@@ -24,7 +24,10 @@
 //     reduction, one partial per workgroup;
 //   * M step + convergence statistics run on the device; a `done` word set by the last
 //     workgroup of the M step freezes theta at exactly the reference's stopping round while the
-//     host only polls it every few rounds (no per-round host sync).
+//     host only polls it every few rounds (no per-round host sync);
+//   * the units of the layout stand in up to three groups (compact / a few ids outside their window / split rows), and the three EM
+//     loops of rsem_em_run (kernel sequence, statistics on a second stream, one launch per round) deal them to launches each in its
+//     own way: unit_groups.hpp is where that dealing is written down; launch_lane below is the one launch site of the lane kernel.
 // MFMA is not used: ~2 flops per 12 bytes, the bound is HBM bandwidth.
 #include <climits>
 #include <cstdlib>
@@ -35,10 +38,13 @@
 #include "em_internal.hpp"
 #include "upload.hpp"
 #include "sell_layout.hpp"
+#include "unit_groups.hpp"
 
 namespace {
 
 using rsem::kEpsilon;
+using rsem::LanePlan;
+using rsem::Loop;
 
 constexpr int kReduceBlocks = 64;   // partial sums of the M step
 constexpr int kMaxTimedRounds = 4096;
@@ -345,7 +351,7 @@ __global__ __launch_bounds__(kBlock) void k_far_colsum(uint64_t n_far, const int
     }
 }
 
-// (Variant LANE, the default: k_estep_lane below; its per-wave body is estep_block.hpp, included above.)
+// (k_estep_lane below; its per-wave body is estep_block.hpp, included above.)
 // The one-kernel round (kSolo, rsem_em_run's default loop): besides their E-step work for round r, some workgroups close
 // a slice of round r-1 -- convergence statistics of theta_{r-1} (buffer `theta`) against theta_{r-2} (buffer `prev`),
 // EM.cpp:400-416 -- and clears that slice of `prev`, which is the buffer round r+1 accumulates into.  The last closer
@@ -483,7 +489,7 @@ __global__ __launch_bounds__(kBlock) void k_solo_finish(int32_t M, double N0, co
 #define RSEM_FQ_DEPTH 3
 #endif
 constexpr int kFarQDepth = RSEM_FQ_DEPTH;  // register sets of the far-queue loop: loads two slices ahead, theta of far ids one slice ahead
-// kFQ: the launch over the units with ids outside their window (Unit::pad[0]; launch_estep deals them to a launch of their own): partial
+// kFQ: the launch over the units with ids outside their window (Unit::pad[0]; unit_groups.hpp deals them to a launch of their own): partial
 // counts for such ids queue up in LDS per wave (FarQueue, estep_block.hpp) -- 18 KB more per workgroup, three workgroups per CU
 // instead of four, which is why the compact units are not launched with it.
 template <bool kFC, bool kSolo = false, bool kFQ = false>
@@ -641,65 +647,6 @@ __global__ __launch_bounds__(kBlock) void k_mstep_reduce(int32_t M, double N0, d
     double t = block_sum_det(v);
     if (threadIdx.x == 0) partials[blockIdx.x] = t;
 }
-
-// theta = counts / sum (EM.cpp:394-398); convergence statistics (EM.cpp:406-413); stop rule
-// (EM.cpp:416) evaluated by the last workgroup to finish.
-__global__ __launch_bounds__(kBlock) void k_mstep_apply(int32_t M, const double* __restrict__ partials,
-                                                         int n_partials, double* counts,
-                                                         const double* __restrict__ theta_old,
-                                                         double* theta_new, double* counts_last, Ctrl* ctrl,
-                                                         int round, int min_round, int max_round) {
-    if (ctrl->done) return;
-    double sum = 0.0;
-    for (int i = 0; i < n_partials; i++) sum += partials[i];
-    int tot = 0;
-    double bmax = 0.0;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i <= M; i += gridDim.x * blockDim.x) {
-        double c = counts[i];
-        double th = c / sum;
-        theta_new[i] = th;
-        counts_last[i] = c;
-        counts[i] = 0.0;
-        double old = theta_old[i];
-        if (old >= 1e-7) {
-            double change = fabs(th - old) / old;
-            if (change >= 0.001) ++tot;
-            bmax = fmax(bmax, change);
-        }
-    }
-    // block reduce
-    __shared__ int s_tot[kBlock / 64];
-    __shared__ double s_b[kBlock / 64];
-    for (int d = 32; d >= 1; d >>= 1) {
-        tot += __shfl_xor(tot, d);
-        bmax = fmax(bmax, __shfl_xor(bmax, d));
-    }
-    if ((threadIdx.x & 63) == 0) { s_tot[threadIdx.x >> 6] = tot; s_b[threadIdx.x >> 6] = bmax; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int i = 1; i < kBlock / 64; i++) { tot += s_tot[i]; bmax = fmax(bmax, s_b[i]); }
-        if (tot) atomicAdd(&ctrl->totNum, tot);
-        atomicMax(&ctrl->bbits, (unsigned long long)__double_as_longlong(bmax));
-        __threadfence();
-        unsigned int t = atomicAdd(&ctrl->ticket, 1u);
-        if (t == gridDim.x - 1) {
-            int totNum = atomicAdd(&ctrl->totNum, 0);
-            unsigned long long bb = atomicMax(&ctrl->bbits, 0ull);
-            ctrl->last_sum = sum;
-            ctrl->last_bchange = __longlong_as_double((long long)bb);
-            ctrl->last_totNum = totNum;
-            ctrl->last_round = round;
-            if (!(round < min_round || (totNum > 0 && round < max_round))) {
-                ctrl->done = 1;
-                ctrl->final_round = round;
-            }
-            atomicExch(&ctrl->totNum, 0);
-            atomicExch(&ctrl->bbits, 0ull);
-            atomicExch(&ctrl->ticket, 0u);
-        }
-    }
-}
-
 
 constexpr int kMstepBlocks = 32;
 
@@ -953,14 +900,13 @@ struct rsem_em_ctx {
     int short_min_units = kShortClassMinUnits;  // ... where the class fills this many units (short_classes_worth_it)
     bool layout_has_q32 = false;      // the current layout was built with Q32 shapes (from the then-current values)
     bool layout_ok = false;           // false between free_layout and a build_layout that went through (a failed rebuild)
-    // LANE variant work list
+    // the lane kernel's work list (dealt to its launches by unit_groups.hpp)
     Unit* d_units = nullptr;
-    unsigned long long* d_trace = nullptr;  // per-workgroup timestamps (tune_unit_order, rsem_em_debug_trace)
     std::vector<Unit> h_units;
     uint64_t long_nnz = 0;  // alignments of the reads left in the CSR
     uint32_t* d_rank = nullptr;  // caller row -> sorted row (inverse of L.d_order), built on first use (em_planes_view)
     double *d_xextra = nullptr, *d_xinv = nullptr;  // split rows: far part of the normaliser / its reciprocal, per row slot from L.x_slot_base
-    int split_rows = 1;          // lay reads with ids outside their window out as split rows (LANE kernel only; option "split_rows")
+    int split_rows = 1;          // lay reads with ids outside their window out as split rows (option "split_rows")
     int split_policy = 1;        // 1: the reads that are mostly outside their window split; 2: every read with an id outside
     uint32_t n_far_units = 0;               // units with an id outside their LDS window (Unit::pad[0])
     unsigned long long n_stray_reads = 0;   // reads the second layout pass sorted apart (sell_build_refined)
@@ -980,7 +926,6 @@ struct rsem_em_ctx {
     hipEvent_t ev_x_fork = nullptr, ev_x_join = nullptr;
     int x_overlap = 0;            // (measured: +4 % on configs[2] with 10 % cross-gene reads split, -4 % at configs[1]'s size without genes)
     int noise_n = 0;  // workgroups of the last main E-step launch (= valid entries of d_noise_a)
-    size_t noise_cap = 0;
     // EM state
     double* d_theta[2] = {nullptr, nullptr};
     double* d_red3 = nullptr;     // three buffers of [counts (M+1) | totals (2 * kTotSlots)] (the fused loop rotates them)
@@ -990,13 +935,11 @@ struct rsem_em_ctx {
     double* d_noise_a = nullptr;  // per-workgroup noise partials of the main E-step launch
     double* d_noise_b = nullptr;  // ... of the long-row launch
     double* d_totals = nullptr;   // = d_red + M + 1: kTotSlots slots of the noise fraction, then of the reads with a non-zero normaliser
-    bool use_totals = false;
     double* d_partials = nullptr;
     double* d_w = nullptr;        // expected-weights scratch (nnz), lazily allocated
     double* d_wn = nullptr;
     Ctrl* d_ctrl = nullptr;
-    int grid_main = 0, grid_long = 0, grid_apply = 0;
-    int kernel = RSEM_EM_KERNEL_AUTO;
+    int grid_long = 0;
     uint32_t forced_T = 0;
     int check_every = 64;
     int n_cus = 256;
@@ -1017,31 +960,22 @@ struct rsem_em_ctx {
 
 namespace {
 
-int resolved_kernel(const rsem_em_ctx* c) {
-    return c->kernel == RSEM_EM_KERNEL_AUTO ? RSEM_EM_KERNEL_LANE : c->kernel;
-}
-
 // (field by field: a copy of a Unit need not keep the 4 padding bytes in front of its Shape)
 bool same_unit(const Unit& a, const Unit& b) {
     return a.shape == b.shape && a.slice_begin == b.slice_begin && a.n_slices == b.n_slices && a.per_wave == b.per_wave && a.base == b.base &&
            a.span == b.span && a.pad[0] == b.pad[0] && a.pad[1] == b.pad[1] && !memcmp(&a.S, &b.S, sizeof(Shape));
 }
 
-// the units of the split rows' shapes behind all the others (both parts keep their order), host and device copy
+// The unit table in the three groups of unit_groups.hpp: the units of the split rows' shapes behind all the others, and the queued
+// main units behind the compact ones where they get a launch of their own (every part keeps its order); host and device copy.
 int partition_units(rsem_em_ctx* c) {
     auto is_main = [](const Unit& u) { return u.S.fmt != kFmtF64X; };
     const auto mid = std::stable_partition(c->h_units.begin(), c->h_units.end(), is_main);
     c->n_units_main = (uint32_t)(mid - c->h_units.begin());
-    // The far-queue launch takes the units with FEW entries outside their window per slice -- reads of a gene that also hit a couple of
-    // transcripts elsewhere: the queue then empties every few slices; a unit of reads without a gene, half of whose entries are
-    // outside, would empty it before every slice and is better off with its atomics inline (configs[1]'s size without genes: 0.634
-    // against 0.650 ms, profiles/r06g_xrows_probe.log) -- and only where such units are worth a launch of their own (one unit in
-    // twenty-five; configs[2] itself has 53 among 3 903 and paid 1 % for the second stream).
-    auto queued = [](const Unit& u) { return u.pad[0] != 0 && (uint64_t)u.pad[1] <= 48ull * u.n_slices; };
+    auto queued = [](const Unit& u) { return rsem::unit_queued(u.pad[0], u.pad[1], u.n_slices); };
     c->n_units_queued = (uint32_t)std::count_if(c->h_units.begin(), mid, queued);
     c->n_units_compact = c->n_units_main;
-    // (moved behind the others only where they get that launch: otherwise every unit keeps its place in the longest-first order)
-    if (c->far_queue && c->n_units_queued * 25ull >= c->n_units_main && c->n_units_queued)
+    if (rsem::far_group_adopted(c->far_queue != 0, c->n_units_queued, c->n_units_main))
         c->n_units_compact = (uint32_t)(std::stable_partition(c->h_units.begin(), mid, [&](const Unit& u) { return !queued(u); }) - c->h_units.begin());
     // the device copy follows every time, so that a unit's index means the same unit on both sides (tune_unit_order reads the
     // trace in device order)
@@ -1051,71 +985,95 @@ int partition_units(rsem_em_ctx* c) {
     return RSEM_OK;
 }
 
-int launch_estep(rsem_em_ctx* c, const double* d_theta, double* d_counts, hipStream_t st, bool use_ctrl) {
+// ---- the lane kernel's launches ---------------------------------------------------------------------------------------------------------
+// What varies between the launches of k_estep_lane; everything else the kernel is handed comes from the context.
+struct LaneIO {
+    const double* theta = nullptr;   // theta, or (FUSED / SOLO: kFC) the previous round's raw counts ...
+    const double* tsrc = nullptr;    // ... and their totals
+    double N0 = 0.0;
+    double* counts = nullptr;
+    double* totals = nullptr;        // the two device-wide totals beside the counts, or nullptr: noise partials per workgroup only
+    unsigned long long* trace = nullptr;  // per-workgroup timestamps, two per unit (tune_unit_order, rsem_em_debug_trace)
+    SoloArgs solo;                   // SOLO: the round the closers close (handed to the launch that carries them, no other)
+    XArgs xa;                        // PLAIN: the split rows' side arrays
+};
+
+// The instantiation a loop takes for its far-queue launch and for its other launches.
+using LaneKernel = decltype(&k_estep_lane<false, false, false>);
+LaneKernel lane_kernel(Loop loop, bool far_queue) {
+    if (loop == Loop::PLAIN) return far_queue ? k_estep_lane<false, false, true> : k_estep_lane<false, false, false>;
+    if (far_queue) return k_estep_lane<true, false, true>;
+    return loop == Loop::SOLO ? k_estep_lane<true, true, false> : k_estep_lane<true, false, false>;
+}
+
+// THE launch of the lane kernel over units [u0, u1): the only place that spells out its argument list.
+void launch_lane(rsem_em_ctx* c, Loop loop, bool far_queue, uint32_t u0, uint32_t u1, hipStream_t s, const LaneIO& io) {
+    if (u1 <= u0) return;
+    const bool closes = loop == Loop::SOLO && !far_queue;
+    hipLaunchKernelGGL(lane_kernel(loop, far_queue), dim3(u1 - u0), dim3(kBlock), 0, s, c->L.d_shapes, c->d_units + u0, c->L.T, c->M, io.theta, io.tsrc,
+                       io.N0, (const unsigned char*)c->d_sval, (const int16_t*)c->d_sexp, c->L.d_ssid, c->d_sncp, c->L.d_masks, io.counts,
+                       c->d_noise_a + u0, io.totals, (const Ctrl*)c->d_ctrl, io.trace ? io.trace + 2 * (size_t)u0 : nullptr,
+                       closes ? io.solo : SoloArgs(), io.xa);
+}
+
+LanePlan plan_lanes(const rsem_em_ctx* c, Loop loop) {
+    rsem::UnitGroups g;
+    g.n = c->n_units; g.n_main = c->n_units_main; g.n_compact = c->n_units_compact;
+    g.far_queue = c->far_queue != 0; g.x_overlap = c->x_overlap != 0; g.split_rows = c->L.n_x_rows != 0; g.stream_x = c->stream_x != nullptr;
+    return rsem::plan_lane_launches(g, loop);
+}
+void launch_planned(rsem_em_ctx* c, const LanePlan& plan, Loop loop, hipStream_t st, const LaneIO& io) {
+    for (int i = 0; i < plan.n; i++) launch_lane(c, loop, plan.at[i].far_queue, plan.at[i].u0, plan.at[i].u1, plan.at[i].second ? c->stream_x : st, io);
+}
+// the second stream (stream_x) beside the caller's: it starts behind what the caller's holds, and the caller's waits for it
+int fork_x(rsem_em_ctx* c, hipStream_t st) {
+    RSEM_HIP_TRY(hipEventRecord(c->ev_x_fork, st));
+    RSEM_HIP_TRY(hipStreamWaitEvent(c->stream_x, c->ev_x_fork, 0));
+    return RSEM_OK;
+}
+int join_x(rsem_em_ctx* c, hipStream_t st) {
+    RSEM_HIP_TRY(hipEventRecord(c->ev_x_join, c->stream_x));
+    RSEM_HIP_TRY(hipStreamWaitEvent(st, c->ev_x_join, 0));
+    return RSEM_OK;
+}
+
+// One E step from a plain theta array (the PLAIN loop and every entry point that runs a single step): the lane launches of
+// unit_groups.hpp between the split rows' two side passes, then the reads left in the CSR.  totals: where the workgroups add the two
+// device-wide totals (rsem_em_run), or nullptr.
+int launch_estep(rsem_em_ctx* c, const double* d_theta, double* d_counts, hipStream_t st, double* d_totals, unsigned long long* d_trace = nullptr) {
     const Ctrl* ctrl = c->d_ctrl;
-    (void)use_ctrl;
     c->noise_n = (int)c->n_units;
-    {
-        XArgs xa;
-        // Up to three groups of units (partition_units): compact [0, nc), with ids outside their window [nc, n_main) -- the far-queue
-        // instantiation, on stream_x beside the compact ones --, split rows [n_main, n) -- between their two side passes; on stream_x
-        // too with option split_overlap.
-        const uint32_t nc = c->n_units_compact, n_main = c->n_units_main, n_all = c->n_units;
-        const bool far_launch = c->far_queue && nc < n_main;
-        const bool x_beside = c->x_overlap && c->L.n_x_rows && n_main > 0 && n_main < n_all;
-        const bool second = c->stream_x && (x_beside || (far_launch && nc > 0));
-        hipStream_t s2 = second ? c->stream_x : st;
-        hipStream_t sx = x_beside ? s2 : st, sf = far_launch ? s2 : st;
-        if (second) {
-            RSEM_HIP_TRY(hipEventRecord(c->ev_x_fork, st));
-            RSEM_HIP_TRY(hipStreamWaitEvent(s2, c->ev_x_fork, 0));
-        }
-        auto lane = [&](uint32_t u0, uint32_t u1, hipStream_t s) {
-            if (u1 > u0)
-                hipLaunchKernelGGL((k_estep_lane<false, false>), dim3(u1 - u0), dim3(kBlock), 0, s, c->L.d_shapes, c->d_units + u0, c->L.T, c->M,
-                                   d_theta, (const double*)nullptr, 0.0, (const unsigned char*)c->d_sval, (const int16_t*)c->d_sexp, c->L.d_ssid,
-                                   c->d_sncp, c->L.d_masks, d_counts, c->d_noise_a + u0, c->use_totals ? c->d_totals : nullptr, ctrl,
-                                   c->d_trace ? c->d_trace + 2 * (size_t)u0 : nullptr, SoloArgs(), xa);
-        };
-        auto lane_fq = [&](uint32_t u0, uint32_t u1, hipStream_t s) {
-            if (u1 > u0)
-                hipLaunchKernelGGL((k_estep_lane<false, false, true>), dim3(u1 - u0), dim3(kBlock), 0, s, c->L.d_shapes, c->d_units + u0, c->L.T, c->M,
-                                   d_theta, (const double*)nullptr, 0.0, (const unsigned char*)c->d_sval, (const int16_t*)c->d_sexp, c->L.d_ssid,
-                                   c->d_sncp, c->L.d_masks, d_counts, c->d_noise_a + u0, c->use_totals ? c->d_totals : nullptr, ctrl,
-                                   c->d_trace ? c->d_trace + 2 * (size_t)u0 : nullptr, SoloArgs(), xa);
-        };
-        if (c->L.n_x_rows) {  // split rows: the far part of their normalisers first
-            xa.extra = c->d_xextra; xa.inv = c->d_xinv; xa.slot_base = c->L.x_slot_base;
-            static const bool batched = !(getenv("RSEM_HIP_ROWSUM_BATCHED") && atoi(getenv("RSEM_HIP_ROWSUM_BATCHED")) == 0);  // measurement knob
-            hipLaunchKernelGGL(batched ? k_far_rowsum<true> : k_far_rowsum<false>, dim3(rsem::ceil_div(c->L.n_x_slots, kBlock)), dim3(kBlock), 0, sx, c->L.n_x_slots,
-                               (const uint64_t*)c->L.d_far_ptr, (const int32_t*)c->L.d_far_sid, (const double*)c->L.d_far_cp, d_theta, c->d_xextra, ctrl);
-        }
-        if (far_launch) lane_fq(nc, n_main, sf);
-        if (!far_launch && sx == st) lane(0, n_all, st);
-        else {
-            lane(0, far_launch ? nc : n_main, st);
-            lane(n_main, n_all, sx);
-        }
-        if (c->L.n_far) {  // ... and their far alignments' fractions afterwards, in transcript order
-            // one step of 4 x 64 entries per wave: the pass is a chain of dependent trips (entries -> theta, reciprocal -> shuffles ->
-            // atomic), and more waves in flight hide more of it than a loop per wave (8 / 16 / 32 workgroups per CU: 335 / 326 /
-            // 312 us at configs[1]'s size without gene structure, the whole grid 294: profiles/r04l_call.log)
-            const int grid = std::max(1, rsem::ceil_div(c->L.n_far, kBlock * 4));
-            static const bool xcd = !(getenv("RSEM_HIP_COLSUM_XCD") && atoi(getenv("RSEM_HIP_COLSUM_XCD")) == 0);  // measurement knob
-            hipLaunchKernelGGL(xcd ? k_far_colsum<true> : k_far_colsum<false>, dim3(grid), dim3(kBlock), 0, sx, c->L.n_far, (const int32_t*)c->L.d_csc_sid,
-                               (const double*)c->L.d_csc_cp, (const uint32_t*)c->L.d_csc_slot, c->L.x_slot_base, d_theta, (const double*)c->d_xinv, d_counts, ctrl);
-        }
-        if (second) {
-            RSEM_HIP_TRY(hipGetLastError());
-            RSEM_HIP_TRY(hipEventRecord(c->ev_x_join, s2));
-            RSEM_HIP_TRY(hipStreamWaitEvent(st, c->ev_x_join, 0));
-        }
+    const LanePlan plan = plan_lanes(c, Loop::PLAIN);
+    hipStream_t sx = plan.x_second ? c->stream_x : st;  // the split rows' chain: rowsum -> their lane launch -> colsum
+    LaneIO io;
+    io.theta = d_theta; io.counts = d_counts; io.totals = d_totals; io.trace = d_trace;
+    if (plan.fork_join) { int rc = fork_x(c, st); if (rc != RSEM_OK) return rc; }
+    if (c->L.n_x_rows) {  // split rows: the far part of their normalisers first
+        io.xa.extra = c->d_xextra; io.xa.inv = c->d_xinv; io.xa.slot_base = c->L.x_slot_base;
+        static const bool batched = !(getenv("RSEM_HIP_ROWSUM_BATCHED") && atoi(getenv("RSEM_HIP_ROWSUM_BATCHED")) == 0);  // measurement knob
+        hipLaunchKernelGGL(batched ? k_far_rowsum<true> : k_far_rowsum<false>, dim3(rsem::ceil_div(c->L.n_x_slots, kBlock)), dim3(kBlock), 0, sx, c->L.n_x_slots,
+                           (const uint64_t*)c->L.d_far_ptr, (const int32_t*)c->L.d_far_sid, (const double*)c->L.d_far_cp, d_theta, c->d_xextra, ctrl);
+    }
+    launch_planned(c, plan, Loop::PLAIN, st, io);
+    if (c->L.n_far) {  // ... and their far alignments' fractions afterwards, in transcript order
+        // one step of 4 x 64 entries per wave: the pass is a chain of dependent trips (entries -> theta, reciprocal -> shuffles ->
+        // atomic), and more waves in flight hide more of it than a loop per wave (8 / 16 / 32 workgroups per CU: 335 / 326 /
+        // 312 us at configs[1]'s size without gene structure, the whole grid 294: profiles/r04l_call.log)
+        const int grid = std::max(1, rsem::ceil_div(c->L.n_far, kBlock * 4));
+        static const bool xcd = !(getenv("RSEM_HIP_COLSUM_XCD") && atoi(getenv("RSEM_HIP_COLSUM_XCD")) == 0);  // measurement knob
+        hipLaunchKernelGGL(xcd ? k_far_colsum<true> : k_far_colsum<false>, dim3(grid), dim3(kBlock), 0, sx, c->L.n_far, (const int32_t*)c->L.d_csc_sid,
+                           (const double*)c->L.d_csc_cp, (const uint32_t*)c->L.d_csc_slot, c->L.x_slot_base, d_theta, (const double*)c->d_xinv, d_counts, ctrl);
+    }
+    if (plan.fork_join) {
+        RSEM_HIP_TRY(hipGetLastError());
+        int rc = join_x(c, st);
+        if (rc != RSEM_OK) return rc;
     }
     RSEM_HIP_TRY(hipGetLastError());
     if (c->L.n_long_rows) {
         hipLaunchKernelGGL(k_estep_long, dim3(c->grid_long), dim3(kBlock), 0, st, (uint64_t)c->L.n_long_rows,
                            (const uint32_t*)(c->L.d_order + c->L.n_sell_rows), (const uint64_t*)c->d_row_ptr, (const int32_t*)c->d_sid, (const double*)c->d_cp,
-                           (const double*)c->d_ncp, d_theta, d_counts, c->d_noise_b, ctrl, c->use_totals ? c->d_totals : nullptr);
+                           (const double*)c->d_ncp, d_theta, d_counts, c->d_noise_b, ctrl, d_totals);
         RSEM_HIP_TRY(hipGetLastError());
     }
     return RSEM_OK;
@@ -1133,21 +1091,9 @@ int launch_weights(rsem_em_ctx* c, const double* d_theta, hipStream_t st) {
     return RSEM_OK;
 }
 
-int launch_mstep(rsem_em_ctx* c, double N0, double* d_counts, const double* d_theta_old, double* d_theta_new,
-                 int round, int min_round, int max_round, hipStream_t st, HostMirror* mirror = nullptr) {
-    const int grid = std::max(1, std::min(kMstepBlocks, rsem::ceil_div((uint64_t)c->M + 1, kBlock * 4)));
-    if (c->use_totals) {
-        const int gridf = std::max(1, std::min(2 * kMstepBlocks, rsem::ceil_div((uint64_t)c->M + 1, kBlock * 2)));
-        hipLaunchKernelGGL(k_mstep_fast<false>, dim3(gridf), dim3(kBlock), 0, st, c->M, N0, d_counts, c->d_totals, d_theta_old, d_theta_new,
-                           c->d_counts_last, c->d_ctrl, round, min_round, max_round, mirror, (double*)nullptr);
-        RSEM_HIP_TRY(hipGetLastError());
-        return RSEM_OK;
-    }
-    hipLaunchKernelGGL(k_mstep_fused, dim3(grid), dim3(kBlock), 0, st, c->M, N0, d_counts, c->d_noise_a, c->noise_n,
-                       c->d_noise_b, n_noise_b(c), c->d_partials, d_theta_old, d_theta_new, c->d_counts_last, c->d_ctrl,
-                       round, min_round, max_round);
-    RSEM_HIP_TRY(hipGetLastError());
-    return RSEM_OK;
+// workgroups of k_mstep_fast (either instantiation)
+int mstep_fast_grid(const rsem_em_ctx* c) {
+    return std::max(1, std::min(2 * kMstepBlocks, rsem::ceil_div((uint64_t)c->M + 1, kBlock * 2)));
 }
 
 int build_layout(rsem_em_ctx* c);
@@ -1239,7 +1185,7 @@ int build_layout(rsem_em_ctx* c) {
     const bool q32 = c->value_bits == 32 && c->have_values;
     std::vector<Unit> units;
     // (not together with Q32 planes: which reads take that format is a documented function of their values alone)
-    int split = c->split_rows && resolved_kernel(c) == RSEM_EM_KERNEL_LANE && !q32;
+    int split = c->split_rows && !q32;
     // (measurement knobs, applied to this build alone: the options keep what the caller set)
     int short_on = c->short_last_plane, short_min_units = c->short_min_units;
     if (const char* e = getenv("RSEM_HIP_SHORT_LAST_PLANE")) short_on = atoi(e) != 0;               // 0 = every plane full
@@ -1288,10 +1234,10 @@ int build_layout(rsem_em_ctx* c) {
     if (const char* e = getenv("RSEM_HIP_TUNE")) c->tune_passes_left = atoi(e);  // tuning knob: 0 disables
     c->n_far_units = 0;
     for (const Unit& u : c->h_units) c->n_far_units += u.pad[0] != 0;
-    // per-workgroup noise partials: enough for any variant's grid
-    c->noise_cap = std::max<size_t>((size_t)c->n_cus * 8, c->n_units);
-    RSEM_HIP_TRY(dmalloc(&c->d_noise_a, c->noise_cap));
-    RSEM_HIP_TRY(hipMemsetAsync(c->d_noise_a, 0, sizeof(double) * c->noise_cap, c->stream));
+    // per-workgroup noise partials
+    const size_t noise_cap = std::max<size_t>((size_t)c->n_cus * 8, c->n_units);
+    RSEM_HIP_TRY(dmalloc(&c->d_noise_a, noise_cap));
+    RSEM_HIP_TRY(hipMemsetAsync(c->d_noise_a, 0, sizeof(double) * noise_cap, c->stream));
 
     c->grid_long = std::max(1, std::min<int>(c->n_cus * 8, rsem::ceil_div(c->L.n_long_rows, kBlock / 64)));  // (k_estep_long: a wave per read)
     c->long_nnz = 0;
@@ -1310,8 +1256,11 @@ int build_layout(rsem_em_ctx* c) {
     return RSEM_OK;
 }
 
-void set_grid_for_kernel(rsem_em_ctx* c) {
-    c->grid_main = std::max(1, std::min<int>(c->n_cus * 8, rsem::ceil_div(c->L.n_slices, kBlock / 64)));
+// an option the layout was built from changed: build it again from the CSR
+int rebuild_layout(rsem_em_ctx* c) {
+    RSEM_HIP_TRY(hipSetDevice(c->device));
+    free_layout(c);
+    return build_layout(c);
 }
 
 }  // namespace
@@ -1392,11 +1341,9 @@ int rsem_em_create(rsem_em_ctx** out, int device, int32_t M, uint64_t N1, uint64
     TRY_OR_FAIL(hipMemsetAsync(c->d_counts, 0, sizeof(double) * ((size_t)M + 1), c->stream));
     TRY_OR_FAIL(hipMemsetAsync(c->d_noise_b, 0, sizeof(double) * c->n_cus * 8, c->stream));
     TRY_OR_FAIL(hipMemsetAsync(c->d_ctrl, 0, sizeof(Ctrl), c->stream));
-    c->grid_apply = std::max(1, std::min(c->n_cus * 2, rsem::ceil_div((uint64_t)M + 1, kBlock)));
     if (const char* e = getenv("RSEM_HIP_T")) c->forced_T = (uint32_t)atoi(e);  // tuning knob: slices per block
     rc = build_layout(c);
     if (rc != RSEM_OK) return fail(rc);
-    set_grid_for_kernel(c);
     rsem::thread_stager().release();
 #undef TRY_OR_FAIL
     *out = c;
@@ -1467,7 +1414,7 @@ int rsem_em_set_option(rsem_em_ctx* c, const char* key, int64_t value) {
     if (!strcmp(key, "release_csr")) {
         // 1: free the caller-order ids and values (12 B per alignment) until something needs them again (then they are read back
         // from the planes: the same doubles).  Refused -- RSEM_ERR_STATE, nothing changed -- where the planes do not hold everything:
-        // Q32 planes, split rows, reads with more than 256 alignments, the CSR kernel, a live model context.  0: bring them back now.
+        // Q32 planes, split rows, reads with more than 256 alignments, a live model context.  0: bring them back now.
         RSEM_REQUIRE(value == 0 || value == 1, "release_csr must be 0 or 1");
         return value ? release_csr(c) : ensure_csr(c);
     }
@@ -1480,15 +1427,7 @@ int rsem_em_set_option(rsem_em_ctx* c, const char* key, int64_t value) {
         // (the thread-per-read and slice-at-a-time kernels of rounds 1-2 left the product in round 6: the checker is oracle/, not a
         // second kernel in the shipped library)
         RSEM_REQUIRE(value == RSEM_EM_KERNEL_AUTO || value == RSEM_EM_KERNEL_LANE, "kernel variants CSR (1) and SELL (2) were retired: AUTO (0) or LANE (3)");
-        c->kernel = (int)value;
-        if (c->layout_ok && c->L.n_x_rows && resolved_kernel(c) != RSEM_EM_KERNEL_LANE) {  // only the LANE kernel walks split rows
-            RSEM_HIP_TRY(hipSetDevice(c->device));
-            free_layout(c);
-            int rc = build_layout(c);
-            if (rc != RSEM_OK) return rc;
-        }
-        set_grid_for_kernel(c);
-        return RSEM_OK;
+        return RSEM_OK;  // (both name the one kernel there is)
     }
     if (!strcmp(key, "split_overlap")) {
         RSEM_REQUIRE(value == 0 || value == 1, "split_overlap must be 0 or 1");
@@ -1500,12 +1439,7 @@ int rsem_em_set_option(rsem_em_ctx* c, const char* key, int64_t value) {
         if (c->split_policy == (int)value) return RSEM_OK;
         c->split_policy = (int)value;
         c->x_overlap = value == 2 ? 1 : 0;
-        RSEM_HIP_TRY(hipSetDevice(c->device));
-        free_layout(c);
-        int rc = build_layout(c);
-        if (rc != RSEM_OK) return rc;
-        set_grid_for_kernel(c);
-        return RSEM_OK;
+        return rebuild_layout(c);
     }
     if (!strcmp(key, "split_rows")) {
         // 1 (default): a read with transcript ids outside the LDS window of its own gene is laid out as a row of its in-window
@@ -1514,12 +1448,7 @@ int rsem_em_set_option(rsem_em_ctx* c, const char* key, int64_t value) {
         RSEM_REQUIRE(value == 0 || value == 1, "split_rows must be 0 or 1");
         if (c->split_rows == (int)value) return RSEM_OK;
         c->split_rows = (int)value;
-        RSEM_HIP_TRY(hipSetDevice(c->device));
-        free_layout(c);
-        int rc = build_layout(c);
-        if (rc != RSEM_OK) return rc;
-        set_grid_for_kernel(c);
-        return RSEM_OK;
+        return rebuild_layout(c);
     }
     if (!strcmp(key, "value_bits") || !strcmp(key, "value_range_bits")) {
         // Format of the value planes the theta-only E step streams (sell_layout.hpp): 64 = the caller's doubles; 32 = a
@@ -1532,12 +1461,7 @@ int rsem_em_set_option(rsem_em_ctx* c, const char* key, int64_t value) {
         if (field == (int)value) return RSEM_OK;
         field = (int)value;
         if (c->value_bits == 64 && !c->layout_has_q32) return RSEM_OK;  // nothing built depends on it
-        RSEM_HIP_TRY(hipSetDevice(c->device));
-        free_layout(c);
-        int rc = build_layout(c);
-        if (rc != RSEM_OK) return rc;
-        set_grid_for_kernel(c);
-        return RSEM_OK;
+        return rebuild_layout(c);
     }
     if (!strcmp(key, "short_last_plane") || !strcmp(key, "short_class_min_units")) {
         // 1 (default): reads whose last value plane is at least a quarter empty are sorted into short classes whose last plane is
@@ -1550,13 +1474,8 @@ int rsem_em_set_option(rsem_em_ctx* c, const char* key, int64_t value) {
         if (field == (int)value) return RSEM_OK;
         field = (int)value;
         if (!sw && !c->short_last_plane) return RSEM_OK;  // nothing built depends on it
-        RSEM_HIP_TRY(hipSetDevice(c->device));
         { int rc0 = ensure_csr(c); if (rc0 != RSEM_OK) return rc0; }
-        free_layout(c);
-        int rc = build_layout(c);
-        if (rc != RSEM_OK) return rc;
-        set_grid_for_kernel(c);
-        return RSEM_OK;
+        return rebuild_layout(c);
     }
     if (!strcmp(key, "check_every")) {
         RSEM_REQUIRE(value >= 1 && value <= kHistCap / 4, "check_every out of range");
@@ -1627,7 +1546,6 @@ int rsem_em_get_info(const rsem_em_ctx* c, const char* key, int64_t* value) {
                            (uint64_t)c->L.n_slices * 8 + (uint64_t)c->n_units * sizeof(Unit) + (uint64_t)w * 16 + 16 * ((uint64_t)c->M + 1)) +
                  (int64_t)(12 * long_nnz + far_bytes);
     }
-    else if (!strcmp(key, "units")) *value = c->n_units;
     else { rsem::set_last_error("unknown info key '%s'", key); return RSEM_ERR_INVALID; }
     return RSEM_OK;
 }
@@ -1636,7 +1554,7 @@ int rsem_em_get_info(const rsem_em_ctx* c, const char* key, int64_t* value) {
 // unit u in dispatch order; *n_units_io in: capacity (units), out: units written.
 int rsem_em_debug_trace(rsem_em_ctx* c, const double* theta, unsigned long long* out, uint32_t* n_units_io) {
     RSEM_REQUIRE(c && theta && out && n_units_io, "NULL argument");
-    RSEM_REQUIRE(resolved_kernel(c) == RSEM_EM_KERNEL_LANE && c->have_values && c->layout_ok, "needs the LANE kernel with values set");
+    RSEM_REQUIRE(c->have_values && c->layout_ok, "needs the LANE kernel with values set");
     RSEM_REQUIRE(*n_units_io >= c->n_units, "trace buffer too small");
     RSEM_HIP_TRY(hipSetDevice(c->device));
     unsigned long long* d = nullptr;
@@ -1644,11 +1562,8 @@ int rsem_em_debug_trace(rsem_em_ctx* c, const double* theta, unsigned long long*
     RSEM_HIP_TRY(hipMemcpyAsync(c->d_theta[0], theta, sizeof(double) * ((size_t)c->M + 1), hipMemcpyHostToDevice, c->stream));
     RSEM_HIP_TRY(hipMemsetAsync(c->d_ctrl, 0, sizeof(Ctrl), c->stream));
     int rc = RSEM_OK;
-    for (int rep = 0; rep < 3 && rc == RSEM_OK; rep++) {  // the last repetition is the one reported (caches warm)
-        c->d_trace = d;
-        rc = launch_estep(c, c->d_theta[0], c->d_counts, c->stream, true);
-        c->d_trace = nullptr;
-    }
+    for (int rep = 0; rep < 3 && rc == RSEM_OK; rep++)  // the last repetition is the one reported (caches warm)
+        rc = launch_estep(c, c->d_theta[0], c->d_counts, c->stream, nullptr, d);
     hipError_t e = hipMemcpyAsync(out, d, sizeof(unsigned long long) * 2 * c->n_units, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipMemsetAsync(c->d_counts, 0, sizeof(double) * ((size_t)c->M + 1), c->stream);
@@ -1687,17 +1602,14 @@ int rsem_em_destroy(rsem_em_ctx* c) {
 static int tune_unit_order(rsem_em_ctx* c, const double* d_theta) {
     while (c->tune_passes_left > 0) {
         --c->tune_passes_left;
-        if (resolved_kernel(c) != RSEM_EM_KERNEL_LANE || c->n_units < 2048) return RSEM_OK;
+        if (c->n_units < 2048) return RSEM_OK;
         const uint32_t n = c->n_units;
         unsigned long long* d = nullptr;
         RSEM_HIP_TRY(hipMalloc((void**)&d, sizeof(unsigned long long) * 2 * n));
         std::vector<unsigned long long> t(2 * (size_t)n);
         int rc = RSEM_OK;
-        for (int rep = 0; rep < 2 && rc == RSEM_OK; rep++) {  // second launch: caches and clocks warm
-            c->d_trace = d;
-            rc = launch_estep(c, d_theta, c->d_counts, c->stream, true);
-            c->d_trace = nullptr;
-        }
+        for (int rep = 0; rep < 2 && rc == RSEM_OK; rep++)  // second launch: caches and clocks warm
+            rc = launch_estep(c, d_theta, c->d_counts, c->stream, nullptr, d);
         hipError_t e = hipMemcpyAsync(t.data(), d, sizeof(unsigned long long) * 2 * n, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         (void)hipFree(d);
@@ -1741,11 +1653,11 @@ __global__ __launch_bounds__(kBlock) void k_solo_close(int M, const double* __re
 // only the one-launch round wins.  RSEM_EM_FUSED=0 / 1 / 2 forces plain / fused / solo (tests run all three).
 // The one-kernel round (SOLO, k_estep_lane<true, true>) needs neither stream hand-off nor M-step kernel and is the default
 // whenever the counts need not cross devices between the E step and theta; RSEM_EM_FUSED=2 asks for it explicitly.
-enum class Loop { PLAIN, FUSED, SOLO };
+// (Loop: unit_groups.hpp, where each loop's dealing of the units to lane launches is written down.)
 Loop loop_wanted(const rsem_em_ctx* c, bool sharded) {
     // (split rows take the kernel sequence: their two side passes stand before and after the lane kernel, which then reads
     // theta as a plain array)
-    const bool possible = resolved_kernel(c) == RSEM_EM_KERNEL_LANE && c->L.n_long_rows == 0 && c->n_units > 0 && c->L.n_x_rows == 0;
+    const bool possible = c->L.n_long_rows == 0 && c->n_units > 0 && c->L.n_x_rows == 0;
     if (!possible) return Loop::PLAIN;
     const char* e = getenv("RSEM_EM_FUSED");
     if (e && !strcmp(e, "0")) return Loop::PLAIN;
@@ -1773,8 +1685,6 @@ int rsem_em_run(rsem_em_ctx* c, double* theta, double N0, int round0, int min_ro
     }
     RSEM_HIP_TRY(hipMemsetAsync(c->d_counts, 0, nb, st));
     RSEM_HIP_TRY(hipMemsetAsync(c->d_totals, 0, sizeof(double) * 2 * kTotSlots, st));
-    c->use_totals = resolved_kernel(c) == RSEM_EM_KERNEL_LANE;  // E-step workgroups also feed the two device-wide totals
-    struct TotalsOff { rsem_em_ctx* c; ~TotalsOff() { c->use_totals = false; } } totals_off{c};
     const int timed = prof ? std::min(max_round - round0, kMaxTimedRounds) : 0;
     if (prof) {
         while ((int)c->events.size() < 2 * timed + 2) {
@@ -1792,17 +1702,14 @@ int rsem_em_run(rsem_em_ctx* c, double* theta, double N0, int round0, int min_ro
     // after the device set its stop flag return at once (theta is frozen at exactly the reference's stopping round).
     // With a communicator the enqueued collectives must be the same on every rank, so there the decision is taken at
     // fixed rounds from the device flag itself (identical on all ranks: they reduce to the same bits).
-    HostMirror* mir = c->use_totals ? c->mirror : nullptr;
-    if (mir) {
-        mir->done = 0;
-        mir->final_round = 0;
-        mir->last_round = round0;
-    }
+    HostMirror* mir = c->mirror;
+    mir->done = 0;
+    mir->final_round = 0;
+    mir->last_round = round0;
     const bool sharded = rsem::comm_active(c->comm);
-    if (sharded && !c->use_totals) { rsem::set_last_error("sharded EM needs the LANE kernel"); return RSEM_ERR_STATE; }
     int printed = round0, lag = 0;
     auto report = [&](int upto) {  // the reference prints this line after every round (EM.cpp:415)
-        if (!mir || !c->progress) return;
+        if (!c->progress) return;
         for (int q = printed + 1; q <= upto; q++) {
             const RoundStat& rs = mir->hist[(q - 1) % kHistCap];
             c->progress(rs.round, rs.sum, rs.bchange, rs.totNum, c->progress_user);
@@ -1815,7 +1722,7 @@ int rsem_em_run(rsem_em_ctx* c, double* theta, double N0, int round0, int min_ro
     // reads buffer (r-1) % 3, accumulates into r % 3; the statistics kernel of round r clears (r-1) % 3 for round r+2,
     // which therefore waits for it (and so also sees its stop flag; the one E step launched past the stopping round only
     // accumulates into a buffer nobody reads).  theta, counts_last and the ROUND lines come from the statistics kernels.
-    const Loop loop = mir ? loop_wanted(c, sharded) : Loop::PLAIN;
+    const Loop loop = loop_wanted(c, sharded);
     const bool fused = loop == Loop::FUSED, solo = loop == Loop::SOLO;
     // The instantiations that take theta out of the previous round's counts (kFC) walk F64X rows as plain F64: no far part, no
     // reciprocal stored.  loop_wanted() does not pick them for a layout with split rows; whoever adds another way here meets this.
@@ -1859,24 +1766,12 @@ int rsem_em_run(rsem_em_ctx* c, double* theta, double N0, int round0, int min_ro
                     hipLaunchKernelGGL(k_solo_close, dim3(std::min<uint32_t>(c->n_units, (uint32_t)kCloseMax)), dim3(kBlock), 0, st, c->M, (const double*)src, N0,
                                        (const Ctrl*)c->d_ctrl, sa);
             } else {
-                // the units with ids outside their window: a launch of their own (far-queue instantiation) beside the compact ones, on
-                // stream_x; the closers ride on the compact launch
-                const uint32_t nc = c->n_units_compact;
-                const bool far_launch = c->far_queue && nc < c->n_units && nc > 0 && c->stream_x;
-                if (far_launch) {
-                    RSEM_HIP_TRY(hipEventRecord(c->ev_x_fork, st));
-                    RSEM_HIP_TRY(hipStreamWaitEvent(c->stream_x, c->ev_x_fork, 0));
-                    hipLaunchKernelGGL((k_estep_lane<true, false, true>), dim3(c->n_units - nc), dim3(kBlock), 0, c->stream_x, c->L.d_shapes, c->d_units + nc, c->L.T, c->M,
-                                       (const double*)src, (const double*)(src + c->M + 1), N0, (const unsigned char*)c->d_sval, (const int16_t*)c->d_sexp, c->L.d_ssid, c->d_sncp, c->L.d_masks, dst,
-                                       c->d_noise_a + nc, dst + c->M + 1, (const Ctrl*)c->d_ctrl, (unsigned long long*)nullptr, SoloArgs());
-                }
-                hipLaunchKernelGGL((k_estep_lane<true, true>), dim3(far_launch ? nc : c->n_units), dim3(kBlock), 0, st, c->L.d_shapes, c->d_units, c->L.T, c->M,
-                                   (const double*)src, (const double*)(src + c->M + 1), N0, (const unsigned char*)c->d_sval, (const int16_t*)c->d_sexp, c->L.d_ssid, c->d_sncp, c->L.d_masks, dst,
-                                   c->d_noise_a, dst + c->M + 1, (const Ctrl*)c->d_ctrl, (unsigned long long*)nullptr, sa);
-                if (far_launch) {
-                    RSEM_HIP_TRY(hipEventRecord(c->ev_x_join, c->stream_x));
-                    RSEM_HIP_TRY(hipStreamWaitEvent(st, c->ev_x_join, 0));
-                }
+                LaneIO io;
+                io.theta = src; io.tsrc = src + c->M + 1; io.N0 = N0; io.counts = dst; io.totals = dst + c->M + 1; io.solo = sa;
+                const LanePlan plan = plan_lanes(c, Loop::SOLO);
+                if (plan.fork_join && (rc = fork_x(c, st)) != RSEM_OK) return rc;
+                launch_planned(c, plan, Loop::SOLO, st, io);
+                if (plan.fork_join && (rc = join_x(c, st)) != RSEM_OK) return rc;
             }
             RSEM_HIP_TRY(hipGetLastError());
             if (prof && ti < timed) RSEM_HIP_TRY(hipEventRecord(c->events[3 + 2 * ti], st));
@@ -1885,18 +1780,9 @@ int rsem_em_run(rsem_em_ctx* c, double* theta, double N0, int round0, int min_ro
             double* dst = c->d_red3 + (size_t)(r % 3) * R;
             if (r - round0 >= 3) RSEM_HIP_TRY(hipStreamWaitEvent(st, c->ev_s[(r - 2) & 3], 0));  // dst was cleared by round r-2's statistics
             if (prof && ti < timed) RSEM_HIP_TRY(hipEventRecord(c->events[2 + 2 * ti], st));
-            {
-                // (as in the one-launch loop: with no compact unit at all, one launch of all units, their far ids inline)
-                const uint32_t nc = c->n_units_compact;
-                const bool far_launch = c->far_queue && nc < c->n_units && nc > 0 && c->stream_x;
-                hipLaunchKernelGGL((k_estep_lane<true, false>), dim3(far_launch ? nc : c->n_units), dim3(kBlock), 0, st, c->L.d_shapes, c->d_units, c->L.T, c->M,
-                                   (const double*)src, (const double*)(src + c->M + 1), N0, (const unsigned char*)c->d_sval, (const int16_t*)c->d_sexp, c->L.d_ssid, c->d_sncp, c->L.d_masks, dst,
-                                   c->d_noise_a, dst + c->M + 1, (const Ctrl*)c->d_ctrl, (unsigned long long*)nullptr, SoloArgs());
-                if (far_launch)  // (this loop keeps its second stream for the statistics: the far units follow on the same stream)
-                    hipLaunchKernelGGL((k_estep_lane<true, false, true>), dim3(c->n_units - nc), dim3(kBlock), 0, st, c->L.d_shapes, c->d_units + nc, c->L.T, c->M,
-                                       (const double*)src, (const double*)(src + c->M + 1), N0, (const unsigned char*)c->d_sval, (const int16_t*)c->d_sexp, c->L.d_ssid, c->d_sncp, c->L.d_masks, dst,
-                                       c->d_noise_a + nc, dst + c->M + 1, (const Ctrl*)c->d_ctrl, (unsigned long long*)nullptr, SoloArgs());
-            }
+            LaneIO io;
+            io.theta = src; io.tsrc = src + c->M + 1; io.N0 = N0; io.counts = dst; io.totals = dst + c->M + 1;
+            launch_planned(c, plan_lanes(c, Loop::FUSED), Loop::FUSED, st, io);
             RSEM_HIP_TRY(hipGetLastError());
             if (prof && ti < timed) RSEM_HIP_TRY(hipEventRecord(c->events[3 + 2 * ti], st));
             if (sharded) {  // EM.cpp:385-389 across shards
@@ -1905,30 +1791,30 @@ int rsem_em_run(rsem_em_ctx* c, double* theta, double N0, int round0, int min_ro
             }
             RSEM_HIP_TRY(hipEventRecord(c->ev_e[r & 3], st));
             RSEM_HIP_TRY(hipStreamWaitEvent(st2, c->ev_e[r & 3], 0));
-            const int gridf = std::max(1, std::min(2 * kMstepBlocks, rsem::ceil_div((uint64_t)c->M + 1, kBlock * 2)));
-            hipLaunchKernelGGL(k_mstep_fast<true>, dim3(gridf), dim3(kBlock), 0, st2, c->M, N0, dst, dst + c->M + 1, th_old, th_new,
+            hipLaunchKernelGGL(k_mstep_fast<true>, dim3(mstep_fast_grid(c)), dim3(kBlock), 0, st2, c->M, N0, dst, dst + c->M + 1, th_old, th_new,
                                c->d_counts_last, c->d_ctrl, r, min_round, max_round, mir, src);
             RSEM_HIP_TRY(hipGetLastError());
             RSEM_HIP_TRY(hipEventRecord(c->ev_s[r & 3], st2));
             st_stats = st2;
         } else {
             if (prof && ti < timed) RSEM_HIP_TRY(hipEventRecord(c->events[2 + 2 * ti], st));
-            rc = launch_estep(c, th_old, c->d_counts, st, true);
+            rc = launch_estep(c, th_old, c->d_counts, st, c->d_totals);
             if (rc != RSEM_OK) return rc;
             if (prof && ti < timed) RSEM_HIP_TRY(hipEventRecord(c->events[3 + 2 * ti], st));
             if (sharded) {  // EM.cpp:385-389 across shards: counts and the two totals in one all-reduce
                 rc = rsem::comm_allreduce_sum_f64(c->comm, c->d_red, R, st);
                 if (rc != RSEM_OK) return rc;
             }
-            rc = launch_mstep(c, N0, c->d_counts, th_old, th_new, r, min_round, max_round, st, mir);
-            if (rc != RSEM_OK) return rc;
+            hipLaunchKernelGGL(k_mstep_fast<false>, dim3(mstep_fast_grid(c)), dim3(kBlock), 0, st, c->M, N0, c->d_counts, c->d_totals, th_old, th_new,
+                               c->d_counts_last, c->d_ctrl, r, min_round, max_round, mir, (double*)nullptr);
+            RSEM_HIP_TRY(hipGetLastError());
         }
         const bool checkpoint = ((r - round0) % c->check_every == 0) || r == last_launch;
-        if (sharded || !mir) {
+        if (sharded) {
             if (r >= min_round && checkpoint) {
                 RSEM_HIP_TRY(hipMemcpyAsync(&h, c->d_ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, st_stats));
                 RSEM_HIP_TRY(hipStreamSynchronize(st_stats));
-                if (mir) report(h.done ? h.final_round : r);
+                report(h.done ? h.final_round : r);
                 if (h.done) break;
             }
             continue;
@@ -1993,10 +1879,13 @@ int rsem_em_step(rsem_em_ctx* c, const double* theta, double N0, double* counts,
     RSEM_HIP_TRY(hipMemcpyAsync(c->d_theta[0], theta, nb, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemsetAsync(c->d_ctrl, 0, sizeof(Ctrl), st));
     RSEM_HIP_TRY(hipMemsetAsync(c->d_counts, 0, nb, st));
-    int rc = launch_estep(c, c->d_theta[0], c->d_counts, st, true);
+    int rc = launch_estep(c, c->d_theta[0], c->d_counts, st, nullptr);
     if (rc != RSEM_OK) return rc;
-    rc = launch_mstep(c, N0, c->d_counts, c->d_theta[0], c->d_theta[1], 1, 1, 1, st);
-    if (rc != RSEM_OK) return rc;
+    // (round 1 of 1: the M step reduces the per-workgroup noise partials itself)
+    const int grid = std::max(1, std::min(kMstepBlocks, rsem::ceil_div((uint64_t)c->M + 1, kBlock * 4)));
+    hipLaunchKernelGGL(k_mstep_fused, dim3(grid), dim3(kBlock), 0, st, c->M, N0, c->d_counts, c->d_noise_a, c->noise_n, c->d_noise_b, n_noise_b(c),
+                       c->d_partials, (const double*)c->d_theta[0], c->d_theta[1], c->d_counts_last, c->d_ctrl, 1, 1, 1);
+    RSEM_HIP_TRY(hipGetLastError());
     Ctrl h;
     RSEM_HIP_TRY(hipMemcpyAsync(&h, c->d_ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, st));
     if (counts) RSEM_HIP_TRY(hipMemcpyAsync(counts, c->d_counts_last, nb, hipMemcpyDeviceToHost, st));
@@ -2022,7 +1911,7 @@ int rsem_em_expected_weights(rsem_em_ctx* c, const double* theta, double N0, dou
     RSEM_HIP_TRY(hipMemsetAsync(c->d_ctrl, 0, sizeof(Ctrl), st));
     RSEM_HIP_TRY(hipMemsetAsync(c->d_counts, 0, nb, st));
     // counts: the main E-step kernel (same launch as every theta-only round); weights: their own file-order pass
-    int rc = launch_estep(c, c->d_theta[0], c->d_counts, st, true);
+    int rc = launch_estep(c, c->d_theta[0], c->d_counts, st, nullptr);
     if (rc != RSEM_OK) return rc;
     hipLaunchKernelGGL(k_mstep_reduce, dim3(kReduceBlocks), dim3(kBlock), 0, st, c->M, N0, c->d_counts, c->d_noise_a, c->noise_n,
                        c->d_noise_b, n_noise_b(c), c->d_partials, (const Ctrl*)c->d_ctrl);

@@ -1,9 +1,11 @@
 """Which units of the sliced layout go to which E-step launch, under every EM loop.
 
-partition_units (em.hip) deals the units of the LANE kernel to up to three launches: the compact units [0, units_compact), the
-units with a few ids outside their LDS window [units_compact, units_main) -- the far-queue instantiation, taken only where they
-are at least one main unit in 25 --, and the split rows [units_main, units).  rsem_em_run launches these ranges its own way in
-each of its three loops (RSEM_EM_FUSED = 0 kernel sequence, 1 statistics on a second stream, 2 one launch per round).  The
+partition_units (em.hip, by the rules of unit_groups.hpp) puts the units of the lane kernel in up to three groups: the compact
+units [0, units_compact), the units with a few ids outside their LDS window [units_compact, units_main) -- the far-queue
+instantiation, taken only where they are at least one main unit in 25 --, and the split rows [units_main, units).
+plan_lane_launches (unit_groups.hpp; enumerated without a GPU by test_unit_groups_cpu.py) deals these ranges to launches its own
+way for each of rsem_em_run's three loops (RSEM_EM_FUSED = 0 kernel sequence, 1 statistics on a second stream, 2 one launch per
+round).  The
 inputs here are built by hand so that each lands in one grouping, G0-G7; every test first asserts the grouping through the
 info keys (a layout change that moves an input elsewhere fails here instead of quietly testing something else), then the
 step against the oracle, whole runs of all three loops against the oracle and each other, and that the host and the device
@@ -108,7 +110,7 @@ INPUTS = {
     "G6": [("single", 2000 * 512), ("apart", 90 * 128)],     # >= 2048 units: tune_unit_order runs on the first run()
     "G7": [("outside", 256)],                                # split rows only (Q32: whole reads, far units run inline)
 }
-_DATA, _ORACLE = {}, {}
+_DATA, _ORACLE, _WEIGHTS = {}, {}, {}
 
 
 def _input(g):
@@ -215,6 +217,50 @@ def test_grouping_step_and_every_loop(g, far_queue, bits, monkeypatch):
     # after the runs (G6: after the measured-lifetime reordering of the first one) the same grouping, the same tables
     _assert_grouping(g, _info(ctx, tag + " after the runs"), far_queue, bits)
     _check_step(ctx, d, oracle, tag)
+    ctx.close()
+
+
+def _oracle_weights(g):
+    if g not in _WEIGHTS:
+        d = _input(g)
+        _WEIGHTS[g] = orc.em_estep(d["M"], d["row_ptr"], d["sid"], d["conprb"], d["ncp"], d["theta0"], want_weights=True)[1:]
+    return _WEIGHTS[g]
+
+
+@pytest.mark.parametrize("g", ["G2", "G4"])
+def test_entry_points_in_turn_on_one_context(g, monkeypatch):
+    """run -> step -> expected_weights -> run on ONE context, under each loop: only run() has the E-step workgroups add the two
+    device-wide totals (it hands the lane launches the totals' address; the other entry points hand them none and reduce the
+    per-workgroup noise partials), and all of them share the counts / totals scratch.  Totals left behind by a run, or scratch not
+    left as the next entry point expects it, would show in the step's sum and theta or in the second run.  G2: three lane launches
+    per round; G4: split rows, every loop falls back to the kernel sequence."""
+    d = _input(g)
+    oc, oth, orounds, ot = _oracle(g, 64)
+    ow, own = _oracle_weights(g)
+    N1 = len(d["row_ptr"]) - 1
+    ctx = _ctx(d)
+    _assert_grouping(g, _info(ctx, g))
+
+    def run(tag):
+        out = ctx.run(d["theta0"], d["N0"], max_round=MAX_ROUND)
+        assert out["rounds"] == orounds and out["totNum"] == ot, (tag, out["rounds"], orounds)
+        assert np.allclose(out["theta"], oth, rtol=1e-6, atol=1e-12), tag
+        return out
+
+    for loop in ("0", "1", "2"):
+        monkeypatch.setenv("RSEM_EM_FUSED", loop)
+        tag = "%s loop %s" % (g, loop)
+        first = run(tag + " first run")
+        counts, theta_new, s, _, _ = ctx.step(d["theta0"], d["N0"])
+        assert np.allclose(counts, oc, rtol=1e-9, atol=1e-9), tag
+        assert abs(s - (d["N0"] + N1)) < 1e-6, (tag, s)
+        assert np.allclose(theta_new, oc / oc.sum(), rtol=1e-9, atol=1e-12), tag
+        c2, w, wn = ctx.expected_weights(d["theta0"], d["N0"])
+        assert np.allclose(c2, oc, rtol=1e-9, atol=1e-9), tag
+        assert np.allclose(w, ow, rtol=1e-12, atol=0) and np.allclose(wn, own, rtol=1e-12, atol=0), tag
+        second = run(tag + " second run")
+        assert np.allclose(second["theta"], first["theta"], rtol=1e-10, atol=1e-18), tag
+    assert ctx.info("unit_tables_agree") == 1
     ctx.close()
 
 
