@@ -323,6 +323,19 @@ int rsem_gibbs_get_pve_c_trans(rsem_gibbs_ctx* ctx, double* pve_c_trans);
  * accumulator sums to rank 0 of `comm` (RCCL over xGMI), replacing the host loop of release() (Gibbs.cpp:372-388).
  * Count vectors need no communication: a rank writes the files of its own chains.  comm is not owned; NULL detaches. */
 int rsem_gibbs_set_comm(rsem_gibbs_ctx* ctx, rsem_comm* comm);
+/* Test aid (not part of the reference's surface; reads only): the read order of the PARALLEL sampler's layout, built now
+ * if it is not yet.  The sampler keys a read's random number by its position in that order.  order[p] = the caller's read
+ * at sorted position p, lg[p] = log2 of the lanes that read takes in the sliced layout (0..6), or RSEM_GIBBS_ORDER_LONG for
+ * the reads that stay in the CSR (more than 256 non-noise items: positions n_sell_rows .. N1-1).  order, lg: N1 entries. */
+#define RSEM_GIBBS_ORDER_LONG 255
+int rsem_gibbs_debug_order(rsem_gibbs_ctx* ctx, uint32_t* order, uint8_t* lg, uint32_t* n_sell_rows);
+/* ... and how the sweep kernel walks it (reads only): *T = slices per block; *n_units_io = capacity of `out` in, units of the
+ * layout out; out (may be NULL: count only) takes 6 words per unit = one workgroup: first slice within its shape, slices,
+ * slices per wave (wave w walks [first + w * per_wave, + per_wave), cut at the unit's end; block b of a shape = its slices
+ * [b * T, b * T + T)), 1 if an id of the unit lies outside its LDS window (the kernel's far path), lg and K of the shape.
+ * The environment variable RSEM_GIBBS_LAYOUT_T (a whole number in 4..256; anything else makes building the layout fail with
+ * RSEM_ERR_INVALID), read when the layout is built, sets T (a measurement / test knob). */
+int rsem_gibbs_debug_units(rsem_gibbs_ctx* ctx, uint32_t* T, uint32_t* n_units_io, uint32_t* out);
 int rsem_gibbs_destroy(rsem_gibbs_ctx* ctx);
 /* sampling.h:19-44: seeds of the first nchains chains for --seed seed. */
 int rsem_gibbs_chain_seeds(uint32_t seed, int nchains, uint32_t* out);

@@ -10,11 +10,13 @@ LIB_PATH = os.environ.get("RSEM_HIP_LIB") or os.path.join(_HERE, "librsem_hip.so
 
 KERNEL_AUTO, KERNEL_CSR, KERNEL_SELL, KERNEL_LANE = 0, 1, 2, 3
 GIBBS_EXACT, GIBBS_PARALLEL = 0, 1
+GIBBS_ORDER_LONG = 255  # RSEM_GIBBS_ORDER_LONG
 
 _u64p = np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
 _f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
+_u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 
 
@@ -82,6 +84,8 @@ def lib():
         L.rsem_gibbs_run_chains.argtypes = [vp, ci, ci, _u32p, ci, _i32p, ci, ci, vp, _f64p, _f64p, _f64p, _f64p, _f64p, vp, vp]
         L.rsem_gibbs_set_comm.argtypes = [vp, vp]
         L.rsem_gibbs_set_allele_groups.argtypes = [vp, i32, _i32p]
+        L.rsem_gibbs_debug_order.argtypes = [vp, _u32p, _u8p, C.POINTER(C.c_uint32)]
+        L.rsem_gibbs_debug_units.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp]
         L.rsem_gibbs_destroy.argtypes = [vp]
         L.rsem_comm_unique_id.argtypes = [C.c_char_p]
         L.rsem_comm_create.argtypes = [C.POINTER(vp), ci, ci, ci, C.c_char_p]
@@ -212,6 +216,7 @@ class GibbsContext:
     def __init__(self, M, row_ptr, sid, conprb, init_counts, alpha, pseudoC, totc, N0, eel, mw, grp, device=0):
         self.M = int(M)
         self.m = len(grp) - 1
+        self.N1 = len(row_ptr) - 1
         self._h = C.c_void_p()
         alpha = None if alpha is None else np.ascontiguousarray(alpha, np.float64)
         _check(lib().rsem_gibbs_create(C.byref(self._h), device, self.M, len(row_ptr) - 1, len(sid),
@@ -242,6 +247,23 @@ class GibbsContext:
 
     def set_comm(self, comm):
         _check(lib().rsem_gibbs_set_comm(self._h, comm._h if comm is not None else None))
+
+    def debug_order(self):
+        """rsem_gibbs_debug_order: (order, lg, n_sell_rows) of the PARALLEL sampler's layout -- order[p] = the caller's read at
+        sorted position p (the key of its random number), lg[p] = log2 of its lanes, GIBBS_ORDER_LONG for the reads that stay
+        in the CSR (positions n_sell_rows and up)."""
+        order, lg = np.zeros(self.N1, np.uint32), np.zeros(self.N1, np.uint8)
+        n_sell = C.c_uint32()
+        _check(lib().rsem_gibbs_debug_order(self._h, order, lg, C.byref(n_sell)))
+        return order, lg, int(n_sell.value)
+
+    def debug_units(self):
+        """rsem_gibbs_debug_units: (T, units) -- units[u] = (first slice within the shape, slices, slices per wave, far flag, lg, K)."""
+        T, n = C.c_uint32(), C.c_uint32(0)
+        _check(lib().rsem_gibbs_debug_units(self._h, C.byref(T), C.byref(n), None))
+        out = np.zeros((n.value, 6), np.uint32)
+        _check(lib().rsem_gibbs_debug_units(self._h, C.byref(T), C.byref(n), out.ctypes.data))
+        return int(T.value), out
 
     def set_allele_groups(self, ta):
         ta = np.ascontiguousarray(ta, np.int32)

@@ -383,6 +383,7 @@ struct rsem_gibbs_ctx {
     double* d_scp = nullptr;
     double* d_sncp = nullptr;
     Unit* d_units = nullptr;
+    std::vector<Unit> h_units;  // host copy of d_units (rsem_gibbs_debug_units)
     uint32_t n_units = 0;
     double* d_g = nullptr;
     // shared by all chains
@@ -460,6 +461,15 @@ int items_error(int code) {
 // PARALLEL mode's structures, all built on the device from the items CSR
 int ensure_parallel_layout(rsem_gibbs_ctx* c) {
     if (c->have_parallel) return RSEM_OK;
+    uint32_t forced_T = 0;  // measurement / test knob: slices per block (0: chosen from the size of the input, sell_build)
+    if (const char* e = getenv("RSEM_GIBBS_LAYOUT_T")) {
+        // (4..256 only: the layout itself never chooses T < 8, and T < 4 takes unit paths that no test runs the sampler on.
+        // Anything else is an error, not silently the default.)
+        char* end = nullptr;
+        const unsigned long v = strtoul(e, &end, 10);
+        RSEM_REQUIRE(end != e && *end == '\0' && v >= 4 && v <= 256, "RSEM_GIBBS_LAYOUT_T must be a whole number in 4..256");
+        forced_T = (uint32_t)v;
+    }
     hipStream_t st = c->stream;
     const uint64_t N1 = c->N1;
     DevBuf nh, err, tmp;
@@ -493,7 +503,7 @@ int ensure_parallel_layout(rsem_gibbs_ctx* c) {
         RSEM_HIP_TRY(hipGetLastError());
     }
     std::vector<Unit> units;
-    int rc = sell_build_refined(c->L, st, N1, c->M, c->d_row_ptr, c->d_sid, (uint32_t)c->n_cus * 4 * 6 * 5 / 2, 0, nullptr, 0, kGWindow, units,
+    int rc = sell_build_refined(c->L, st, N1, c->M, c->d_row_ptr, c->d_sid, (uint32_t)c->n_cus * 4 * 6 * 5 / 2, forced_T, nullptr, 0, kGWindow, units,
                                 &c->d_units);  // (Unit::pad[0]: ids outside the unit's window)
     if (rc != RSEM_OK) return rc;
     RSEM_HIP_TRY(dmalloc(&c->d_scp, c->L.n_planes * 64));
@@ -502,6 +512,7 @@ int ensure_parallel_layout(rsem_gibbs_ctx* c) {
     if (rc != RSEM_OK) return rc;
     RSEM_HIP_TRY(hipStreamSynchronize(st));
     c->n_units = (uint32_t)units.size();
+    c->h_units = units;
     RSEM_HIP_TRY(dmalloc(&c->d_g, (size_t)c->M + 1));
     if (c->L.n_long_rows == 0) {  // the split CSR was only needed to build the slices
         hipFree(c->d_sid); hipFree(c->d_cp); hipFree(c->d_row_ptr); hipFree(c->d_ncp);
@@ -570,6 +581,44 @@ int rsem_gibbs_get_pve_c_trans(rsem_gibbs_ctx* c, double* out) {
 int rsem_gibbs_set_comm(rsem_gibbs_ctx* c, rsem_comm* comm) {
     RSEM_REQUIRE(c != nullptr, "NULL argument");
     c->comm = comm;
+    return RSEM_OK;
+}
+
+int rsem_gibbs_debug_order(rsem_gibbs_ctx* c, uint32_t* order, uint8_t* lg, uint32_t* n_sell_rows) {
+    RSEM_REQUIRE(c && order && lg && n_sell_rows, "NULL argument");
+    RSEM_HIP_TRY(hipSetDevice(c->device));
+    int rc = ensure_parallel_layout(c);
+    if (rc != RSEM_OK) return rc;
+    const SellLayout& L = c->L;
+    RSEM_REQUIRE((uint64_t)L.n_sell_rows + L.n_long_rows == c->N1, "the layout does not hold every read");
+    if (c->N1) {
+        RSEM_HIP_TRY(hipMemcpyAsync(order, L.d_order, sizeof(uint32_t) * c->N1, hipMemcpyDeviceToHost, c->stream));
+        RSEM_HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    for (uint64_t p = 0; p < c->N1; p++) lg[p] = RSEM_GIBBS_ORDER_LONG;
+    for (int s = 0; s < L.n_shapes; s++) {
+        const Shape& S = L.h_shapes[s];
+        for (uint64_t p = S.row_base; p < (uint64_t)S.row_base + S.n_rows && p < L.n_sell_rows; p++) lg[p] = (uint8_t)S.lg;
+    }
+    *n_sell_rows = L.n_sell_rows;
+    return RSEM_OK;
+}
+
+int rsem_gibbs_debug_units(rsem_gibbs_ctx* c, uint32_t* T, uint32_t* n_units_io, uint32_t* out) {
+    RSEM_REQUIRE(c && T && n_units_io, "NULL argument");
+    RSEM_HIP_TRY(hipSetDevice(c->device));
+    int rc = ensure_parallel_layout(c);
+    if (rc != RSEM_OK) return rc;
+    *T = c->L.T;
+    const uint32_t cap = *n_units_io;
+    *n_units_io = (uint32_t)c->h_units.size();
+    if (!out) return RSEM_OK;
+    RSEM_REQUIRE(cap >= c->h_units.size(), "out holds fewer units than the layout has");
+    for (size_t u = 0; u < c->h_units.size(); u++) {
+        const Unit& U = c->h_units[u];
+        uint32_t* o = out + 6 * u;
+        o[0] = U.slice_begin; o[1] = U.n_slices; o[2] = U.per_wave; o[3] = U.pad[0] != 0; o[4] = (uint32_t)U.S.lg; o[5] = (uint32_t)U.S.K;
+    }
     return RSEM_OK;
 }
 
