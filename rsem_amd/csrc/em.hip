@@ -46,72 +46,19 @@ using rsem::kEpsilon;
 using rsem::LanePlan;
 using rsem::Loop;
 
-constexpr int kReduceBlocks = 64;   // partial sums of the M step
 constexpr int kMaxTimedRounds = 4096;
 constexpr int kWindow = 2048;        // doubles of LDS count window per workgroup (16 KB)
 static_assert(kWindow == kLayoutWindow, "the layout sorts reads apart and sizes windows for the E step's LDS window (sell_layout.hpp)");
 
 constexpr int kTotSlots = 64;  // addresses per device-wide total (E-step workgroups add round-robin)
 
-struct Ctrl {  // device-resident loop control, one per ctx
-    int done;
-    int final_round;
-    int totNum;               // accumulating
-    unsigned int ticket;
-    unsigned int bar;         // grid barrier of the fused M-step kernel
-    unsigned long long bbits; // accumulating max |dtheta|/theta as ordered bits
-    double last_sum;
-    double last_bchange;
-    int last_totNum;
-    int last_round;
-    unsigned long long tick2;  // k_mstep_fast: (sum of totNum) << 32 | arrivals, one atomic per workgroup
-    double fsum;               // closers beyond kSumSlots add here (none with today's launch shapes)
-    // The floating-point sum of the round's counts -- the SUM of the reference's ROUND line -- is put together from one partial sum
-    // per closer, ADDED IN CLOSER ORDER by the last one to arrive: its last digits do not depend on who arrived when.
-    double fslot[1024];
-};
-constexpr int kSumSlots = 1024;
-
-
-// A closer leaves its partial sum in its slot (an exchange: the returned old value is what the arrival that follows is made to
-// depend on, see solo_close_round); the last closer adds the slots up in index order.
-__device__ inline unsigned int sum_slot_put(Ctrl* ctrl, int me, double csum) {
-    double was;
-    if (me < kSumSlots) was = __hip_atomic_exchange(&ctrl->fslot[me], csum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else was = __hip_atomic_fetch_add(&ctrl->fsum, csum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned int z;
-    asm volatile("v_and_b32 %0, 0, %1" : "=v"(z) : "v"((unsigned int)__double_as_longlong(was)));
-    return z;
-}
-__device__ inline double sum_slots_take(Ctrl* ctrl, int n_closers) {
-    double s = 0.0;
-    const int n = n_closers < kSumSlots ? n_closers : kSumSlots;
-    for (int i = 0; i < n; i++) s += __hip_atomic_load(&ctrl->fslot[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (n_closers > kSumSlots) {
-        s += __hip_atomic_load(&ctrl->fsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&ctrl->fsum, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return s;
-}
-
-// What the host reads while the loop runs, in pinned host memory the M-step kernel writes directly (no stream sync, no
-// copy): the statistics line of every finished round (EM.cpp:415) and the stop flag.  hist is a ring; the host keeps
-// fewer than kHistCap rounds in flight.
-constexpr int kHistCap = 1024;
-struct RoundStat { double sum, bchange; int totNum, round; };
-struct HostMirror {
-    int last_round;  // rounds <= last_round have their RoundStat in hist[(round - 1) % kHistCap]
-    int done;
-    int final_round;
-    int pad;
-    RoundStat hist[kHistCap];
-};
-
 
 // ---- E step ----------------------------------------------------------------------------------
 
 // wave_sum and the per-wave body of the LANE kernel (also run on the CPU by tests/estep_emu.cpp)
 #include "estep_block.hpp"
+// Ctrl, HostMirror and the closer of a round (also run on the CPU by tests/round_close_emu.cpp)
+#include "round_close.hpp"
 
 // per-workgroup noise partial (for the callers that reduce the partials themselves) and, when `tot` is given, two
 // device-wide totals: tot[0] += v (noise fraction), tot[1] += u (reads with a non-zero normaliser: an integer
@@ -371,7 +318,7 @@ struct SoloArgs {
 // atomics queued up behind each other (+40 us on either config).  So: kCloseMax workgroups spread evenly over the
 // launch order close a slice each in their PROLOGUE, the whole workgroup taking part, one pair of atomics per closer.
 constexpr int kCloseMax = 128;
-__device__ inline void solo_close_round(const SoloArgs& A, int M, double N0, const double* __restrict__ cur) {
+__device__ inline void solo_close_round(const SoloArgs& A, int M, double N0, const double* __restrict__ cur, CloseScratch* scratch) {
     const int n_close = min((int)gridDim.x, kCloseMax);
     const int stride = (int)gridDim.x / n_close;
     const int rel = (int)blockIdx.x - stride / 2;
@@ -380,95 +327,19 @@ __device__ inline void solo_close_round(const SoloArgs& A, int M, double N0, con
     const int lane = threadIdx.x & 63;
     const int n = M + 1;
     const int per = (n + n_close - 1) / n_close;
-    const int lo = me * per, hi = min(n, lo + per);
-    constexpr int kPre = 8;
-    double pc[kPre], pp[kPre];
-    const bool pre = per <= kPre * kBlock;
-    if (pre) {
-#pragma unroll
-        for (int k = 0; k < kPre; k++) {
-            const int i = lo + (int)threadIdx.x + kBlock * k;
-            pc[k] = i < hi ? cur[i] : 0.0;
-            pp[k] = i < hi ? A.prev[i] : 0.0;
-        }
-    }
+    SliceWalk walk;
+    walk.load(me * per, min(n, me * per + per), kBlock, cur, A.prev);
     const double extra_c = wave_sum(cur[n + lane]) + N0, sum_c = wave_sum(cur[n + kTotSlots + lane]) + N0;
     const double extra_p = wave_sum(A.prev[n + lane]) + N0, sum_p = wave_sum(A.prev[n + kTotSlots + lane]) + N0;
-    int tot = 0;
-    double bmax = 0.0, csum = 0.0;
-    auto one = [&](int i, double craw, double praw) {
-        csum += craw + (i == 0 ? extra_c : 0.0);
-        const double th = (craw + (i == 0 ? extra_c : 0.0)) / sum_c;
-        const double old = (praw + (i == 0 ? extra_p : 0.0)) / sum_p;
+    CloseAcc acc;
+    walk.each(cur, A.prev, [&](int i, double craw, double praw) {
+        const double c = craw + (i == 0 ? extra_c : 0.0);
         A.prev[i] = 0.0;
-        if (old >= 1e-7) {
-            const double change = fabs(th - old) / old;
-            if (change >= 0.001) ++tot;
-            bmax = fmax(bmax, change);
-        }
-    };
-    if (pre) {
-#pragma unroll
-        for (int k = 0; k < kPre; k++) {
-            const int i = lo + (int)threadIdx.x + kBlock * k;
-            if (i < hi) one(i, pc[k], pp[k]);
-        }
-    } else {
-        for (int i = lo + threadIdx.x; i < hi; i += kBlock) one(i, cur[i], A.prev[i]);
-    }
-    for (int d = 32; d >= 1; d >>= 1) {
-        tot += __shfl_xor(tot, d);
-        bmax = fmax(bmax, __shfl_xor(bmax, d));
-    }
-    csum = wave_sum(csum);
-    __shared__ int s_tot[kBlock / 64];
-    __shared__ double s_b[kBlock / 64], s_c[kBlock / 64];
-    if (lane == 0) { s_tot[threadIdx.x >> 6] = tot; s_b[threadIdx.x >> 6] = bmax; s_c[threadIdx.x >> 6] = csum; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int i = 1; i < kBlock / 64; i++) { tot += s_tot[i]; bmax = fmax(bmax, s_b[i]); csum += s_c[i]; }
-        Ctrl* ctrl = A.ctrl;
-        // The arrival must not overtake the maximum.  No fence: an agent-scope fence in the middle of this kernel writes
-        // back and invalidates the XCD's L2 under everybody else's feet.  The arrival's operand is made to depend on the
-        // RETURN of the max instead (one more trip for this thread only).
-        unsigned int zero = 0;
-        if (bmax > 0.0) {
-            const unsigned long long was = __hip_atomic_fetch_max(&ctrl->bbits, (unsigned long long)__double_as_longlong(bmax),
-                                                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            asm volatile("v_and_b32 %0, 0, %1" : "=v"(zero) : "v"((unsigned int)was));
-        }
-        zero += sum_slot_put(ctrl, me, csum);  // this closer's share of the floating-point sum of the counts (the reference's SUM, EM.cpp:394-398,415)
-        const unsigned long long old = __hip_atomic_fetch_add(&ctrl->tick2, (((unsigned long long)(unsigned)tot << 32) | 1ull) + zero,
-                                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((int)(old & 0xffffffffull) == n_close - 1) {  // last closer: stop rule (EM.cpp:416) for round stat_round
-            const int round = A.stat_round;
-            const int totNum = (int)(old >> 32) + tot;
-            const unsigned long long bb = __hip_atomic_load(&ctrl->bbits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const double fsum = sum_slots_take(ctrl, n_close);
-            ctrl->last_sum = fsum;
-            ctrl->last_bchange = __longlong_as_double((long long)bb);
-            ctrl->last_totNum = totNum;
-            ctrl->last_round = round;
-            const bool stop = !(round < A.min_round || (totNum > 0 && round < A.max_round));
-            if (stop) {
-                ctrl->done = 1;
-                ctrl->final_round = round;
-            }
-            if (A.mirror) {
-                RoundStat* h = &A.mirror->hist[(round - 1) % kHistCap];
-                h->sum = fsum;
-                h->bchange = __longlong_as_double((long long)bb);
-                h->totNum = totNum;
-                h->round = round;
-                if (stop) A.mirror->final_round = round;
-                __hip_atomic_store(&A.mirror->last_round, round, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-                if (stop) __hip_atomic_store(&A.mirror->done, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-            __hip_atomic_store(&ctrl->bbits, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&ctrl->tick2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            for (int k = 0; k < 2 * kTotSlots; k++) A.prev[n + k] = 0.0;  // every other closer has read them
-        }
-    }
+        acc.add(c, c / sum_c, (praw + (i == 0 ? extra_p : 0.0)) / sum_p);
+    });
+    close_reduce(acc, scratch);
+    if (threadIdx.x == 0 && close_arrive(A.ctrl, A.mirror, me, n_close, acc, A.stat_round, A.min_round, A.max_round, nullptr))
+        for (int k = 0; k < 2 * kTotSlots; k++) A.prev[n + k] = 0.0;  // the last closer: every other one has read them
 }
 
 // theta and counts of the round the one-kernel loop stopped at, from the buffer that round accumulated (EM.cpp:392-398)
@@ -516,7 +387,8 @@ __global__ __launch_bounds__(kBlock) void k_estep_lane(
         fq.n = fq_n + w;
         if (lane == 0) fq_n[w] = 0;
     }
-    if (kSolo && solo.stat_round > 0) solo_close_round(solo, M, N0, theta);
+    __shared__ CloseScratch close_lds;
+    if (kSolo && solo.stat_round > 0) solo_close_round(solo, M, N0, theta, &close_lds);
     double noise = 0.0, neff = 0.0;
     {
         const Shape& G = U.S;
@@ -614,8 +486,7 @@ __global__ __launch_bounds__(kBlock) void k_estep_lane(
 
 // ---- M step ----------------------------------------------------------------------------------
 
-__device__ inline double block_sum_det(double v) {  // deterministic: fixed tree
-    __shared__ double red[kBlock / 64];
+__device__ inline double block_sum_det(double v, double* red) {  // deterministic: fixed tree; red: kBlock / 64 doubles of LDS
     __syncthreads();
     v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
@@ -625,30 +496,19 @@ __device__ inline double block_sum_det(double v) {  // deterministic: fixed tree
     return t;
 }
 
-// counts[0] += sum(noise partials) + N0 (EM.cpp:392), then per-block partial sums of counts
-__global__ __launch_bounds__(kBlock) void k_mstep_reduce(int32_t M, double N0, double* counts,
-                                                          const double* __restrict__ noise_a, int n_a,
-                                                          const double* __restrict__ noise_b, int n_b,
-                                                          double* partials, const Ctrl* ctrl) {
-    if (ctrl && ctrl->done) return;
-    const int n = M + 1;
-    const int per = (n + gridDim.x - 1) / gridDim.x;
-    const int lo = blockIdx.x * per, hi = min(n, lo + per);
-    if (blockIdx.x == 0) {
-        double v = 0.0;
-        for (int i = threadIdx.x; i < n_a; i += blockDim.x) v += noise_a[i];
-        for (int i = threadIdx.x; i < n_b; i += blockDim.x) v += noise_b[i];
-        double t = block_sum_det(v);
-        if (threadIdx.x == 0) counts[0] = counts[0] + t + N0;
-        __syncthreads();
-    }
+// counts[0] += sum(noise partials) + N0 (EM.cpp:392); one workgroup
+__global__ __launch_bounds__(kBlock) void k_add_noise(double N0, double* counts, const double* __restrict__ noise_a, int n_a,
+                                                       const double* __restrict__ noise_b, int n_b) {
+    __shared__ double red[kBlock / 64];
     double v = 0.0;
-    for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) v += counts[i];
-    double t = block_sum_det(v);
-    if (threadIdx.x == 0) partials[blockIdx.x] = t;
+    for (int i = threadIdx.x; i < n_a; i += blockDim.x) v += noise_a[i];
+    for (int i = threadIdx.x; i < n_b; i += blockDim.x) v += noise_b[i];
+    const double t = block_sum_det(v, red);
+    if (threadIdx.x == 0) counts[0] = counts[0] + t + N0;
 }
 
 constexpr int kMstepBlocks = 32;
+static_assert(kCloseMax <= kSumSlots && 2 * kMstepBlocks <= kSumSlots, "every closer has a slot for its share of the sum");
 
 // Fused M step: one launch, <= 32 co-resident workgroups, one grid barrier.
 //   phase 1: counts[0] += noise partials + N0 (EM.cpp:392); per-workgroup partial sums of counts
@@ -665,16 +525,17 @@ __global__ __launch_bounds__(kBlock) void k_mstep_fused(int32_t M, double N0, do
     const int nb = gridDim.x;
     const int per = (n + nb - 1) / nb;
     const int lo = blockIdx.x * per, hi = min(n, lo + per);
+    __shared__ CloseScratch close_lds;  // (phase 1 reduces through its doubles: the barrier stands between the two uses)
     // phase 1: this workgroup's share of sum(counts) and of the noise partials
     double v = 0.0;
     for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) v += counts[i];
-    const double t_counts = block_sum_det(v);
+    const double t_counts = block_sum_det(v, close_lds.csum);
     const int n_noise = n_a + n_b;
     const int nper = (n_noise + nb - 1) / nb;
     const int nlo = blockIdx.x * nper, nhi = min(n_noise, nlo + nper);
     v = 0.0;
     for (int i = nlo + threadIdx.x; i < nhi; i += blockDim.x) v += (i < n_a) ? noise_a[i] : noise_b[i - n_a];
-    const double t_noise = block_sum_det(v);
+    const double t_noise = block_sum_det(v, close_lds.csum);
     // grid barrier (all workgroups are resident: gridDim <= 32)
     if (threadIdx.x == 0) {
         __hip_atomic_store(&partials[blockIdx.x], t_counts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -700,52 +561,19 @@ __global__ __launch_bounds__(kBlock) void k_mstep_fused(int32_t M, double N0, do
     __syncthreads();
     const double extra0 = s_sum[1] + N0;      // counts[0] += noise + N0 (EM.cpp:392)
     const double sum = s_sum[0] + extra0;
-    int tot = 0;
-    double bmax = 0.0;
+    CloseAcc acc;
     for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
         double c = counts[i] + (i == 0 ? extra0 : 0.0);
         double th = c / sum;
         theta_new[i] = th;
         counts_last[i] = c;
         counts[i] = 0.0;
-        double old = theta_old[i];
-        if (old >= 1e-7) {
-            double change = fabs(th - old) / old;
-            if (change >= 0.001) ++tot;
-            bmax = fmax(bmax, change);
-        }
+        acc.add(c, th, theta_old[i]);
     }
-    __shared__ int s_tot[kBlock / 64];
-    __shared__ double s_b[kBlock / 64];
-    for (int d = 32; d >= 1; d >>= 1) {
-        tot += __shfl_xor(tot, d);
-        bmax = fmax(bmax, __shfl_xor(bmax, d));
-    }
-    if ((threadIdx.x & 63) == 0) { s_tot[threadIdx.x >> 6] = tot; s_b[threadIdx.x >> 6] = bmax; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int i = 1; i < kBlock / 64; i++) { tot += s_tot[i]; bmax = fmax(bmax, s_b[i]); }
-        if (tot) atomicAdd(&ctrl->totNum, tot);
-        atomicMax(&ctrl->bbits, (unsigned long long)__double_as_longlong(bmax));
-        __threadfence();
-        unsigned int tk = atomicAdd(&ctrl->ticket, 1u);
-        if (tk == gridDim.x - 1) {
-            int totNum = atomicAdd(&ctrl->totNum, 0);
-            unsigned long long bb = atomicMax(&ctrl->bbits, 0ull);
-            ctrl->last_sum = sum;
-            ctrl->last_bchange = __longlong_as_double((long long)bb);
-            ctrl->last_totNum = totNum;
-            ctrl->last_round = round;
-            if (!(round < min_round || (totNum > 0 && round < max_round))) {
-                ctrl->done = 1;
-                ctrl->final_round = round;
-            }
-            atomicExch(&ctrl->totNum, 0);
-            atomicExch(&ctrl->bbits, 0ull);
-            atomicExch(&ctrl->ticket, 0u);
-            atomicExch(&ctrl->bar, 0u);
-        }
-    }
+    close_reduce(acc, &close_lds);
+    // (the ROUND line's sum is the barrier's, the one theta was divided by)
+    if (threadIdx.x == 0 && close_arrive(ctrl, nullptr, (int)blockIdx.x, nb, acc, round, min_round, max_round, &sum))
+        RSEM_AGENT_STORE(&ctrl->bar, 0u);  // the last workgroup: everybody has left the barrier
 }
 
 // M step without a grid-wide reduction.  Every read whose normaliser is >= EPSILON contributes fractions that sum to
@@ -775,98 +603,28 @@ __global__ __launch_bounds__(kBlock) void k_mstep_fast(int32_t M, double N0, dou
         if (threadIdx.x == 0) { s_totals[0] = a; s_totals[1] = b; }
     }
     // this workgroup's slice of counts / theta_old is requested first, so it arrives while the partials are reduced
-    constexpr int kPre = 8;
-    const bool pre = (hi - lo) <= kPre * (int)blockDim.x;
-    double pc[kPre], po[kPre];
-    if (pre) {
-#pragma unroll
-        for (int k = 0; k < kPre; k++) {
-            const int i = lo + (int)threadIdx.x + k * (int)blockDim.x;
-            pc[k] = i < hi ? counts[i] : 0.0;
-            po[k] = i < hi ? theta_old[i] : 0.0;
-        }
-    }
+    SliceWalk walk;
+    walk.load(lo, hi, (int)blockDim.x, counts, theta_old);
+    __shared__ CloseScratch close_lds;
+    __shared__ int s_last;
+    if (threadIdx.x == 0) s_last = 0;
     __syncthreads();
     const double extra0 = s_totals[0] + N0;  // counts[0] += noise + N0 (EM.cpp:392)
     const double sum = s_totals[1] + N0;
-    int tot = 0;
-    double bmax = 0.0, csum = 0.0;
-    auto one = [&](int i, double craw, double old) {
+    CloseAcc acc;
+    if (kFused && blockIdx.x == 0 && threadIdx.x < 2 * kTotSlots) spent[n + threadIdx.x] = 0.0;
+    walk.each(counts, theta_old, [&](int i, double craw, double old) {
         const double c = craw + (i == 0 ? extra0 : 0.0);
-        csum += c;
         const double th = c / sum;
         theta_new[i] = th;
         counts_last[i] = c;
         if (kFused) spent[i] = 0.0;
         else counts[i] = 0.0;
-        if (old >= 1e-7) {
-            const double change = fabs(th - old) / old;
-            if (change >= 0.001) ++tot;
-            bmax = fmax(bmax, change);
-        }
-    };
-    if (kFused && blockIdx.x == 0 && threadIdx.x < 2 * kTotSlots) spent[n + threadIdx.x] = 0.0;
-    if (pre) {
-#pragma unroll
-        for (int k = 0; k < kPre; k++) {
-            const int i = lo + (int)threadIdx.x + k * (int)blockDim.x;
-            if (i < hi) one(i, pc[k], po[k]);
-        }
-    } else {
-        for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) one(i, counts[i], theta_old[i]);
-    }
-    __shared__ int s_tot[kBlock / 64];
-    __shared__ double s_b[kBlock / 64], s_c[kBlock / 64];
-    for (int d = 32; d >= 1; d >>= 1) {
-        tot += __shfl_xor(tot, d);
-        bmax = fmax(bmax, __shfl_xor(bmax, d));
-    }
-    csum = wave_sum(csum);
-    __shared__ int s_last;
-    if ((threadIdx.x & 63) == 0) { s_tot[threadIdx.x >> 6] = tot; s_b[threadIdx.x >> 6] = bmax; s_c[threadIdx.x >> 6] = csum; }
-    if (threadIdx.x == 0) s_last = 0;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int i = 1; i < kBlock / 64; i++) { tot += s_tot[i]; bmax = fmax(bmax, s_b[i]); csum += s_c[i]; }
-        // one max, one returning add that carries both this workgroup's count and its arrival; the add follows the max by a
-        // data dependency instead of a fence (see solo_close_round: this kernel runs beside an E step in the fused loop)
-        unsigned int zero = 0;
-        if (bmax > 0.0) {
-            const unsigned long long was = __hip_atomic_fetch_max(&ctrl->bbits, (unsigned long long)__double_as_longlong(bmax),
-                                                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            asm volatile("v_and_b32 %0, 0, %1" : "=v"(zero) : "v"((unsigned int)was));
-        }
-        zero += sum_slot_put(ctrl, (int)blockIdx.x, csum);  // the floating-point sum of the counts, for the ROUND line only (theta divides by the exact `sum` above)
-        const unsigned long long old = __hip_atomic_fetch_add(&ctrl->tick2, (((unsigned long long)(unsigned)tot << 32) | 1ull) + zero,
-                                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((unsigned)(old & 0xffffffffull) == gridDim.x - 1) {  // last workgroup: stop rule (EM.cpp:416)
-            const int totNum = (int)(old >> 32) + tot;
-            const unsigned long long bb = __hip_atomic_load(&ctrl->bbits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const double fsum = sum_slots_take(ctrl, (int)gridDim.x);
-            ctrl->last_sum = fsum;
-            ctrl->last_bchange = __longlong_as_double((long long)bb);
-            ctrl->last_totNum = totNum;
-            ctrl->last_round = round;
-            const bool stop = !(round < min_round || (totNum > 0 && round < max_round));
-            if (stop) {
-                ctrl->done = 1;
-                ctrl->final_round = round;
-            }
-            if (mirror) {  // the host's view: this round's line first, then the counters that announce it
-                RoundStat* h = &mirror->hist[(round - 1) % kHistCap];
-                h->sum = fsum;
-                h->bchange = __longlong_as_double((long long)bb);
-                h->totNum = totNum;
-                h->round = round;
-                if (stop) mirror->final_round = round;
-                __hip_atomic_store(&mirror->last_round, round, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-                if (stop) __hip_atomic_store(&mirror->done, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-            __hip_atomic_store(&ctrl->bbits, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&ctrl->tick2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s_last = 1;
-        }
-    }
+        acc.add(c, th, old);
+    });
+    close_reduce(acc, &close_lds);
+    // (the slots' floating-point sum of the counts is for the ROUND line only: theta divides by the exact `sum` above)
+    if (threadIdx.x == 0 && close_arrive(ctrl, mirror, (int)blockIdx.x, nb, acc, round, min_round, max_round, nullptr)) s_last = 1;
     __syncthreads();
     // the last workgroup to arrive clears the totals for the next round: every workgroup has read them by now
     if (!kFused && s_last && threadIdx.x < 2 * kTotSlots) __hip_atomic_store(&totals[threadIdx.x], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1336,7 +1094,7 @@ int rsem_em_create(rsem_em_ctx** out, int device, int32_t M, uint64_t N1, uint64
         TRY_OR_FAIL(hipEventCreateWithFlags(&c->ev_e[i], hipEventDisableTiming));
         TRY_OR_FAIL(hipEventCreateWithFlags(&c->ev_s[i], hipEventDisableTiming));
     }
-    TRY_OR_FAIL(dmalloc(&c->d_partials, 2 * kReduceBlocks));
+    TRY_OR_FAIL(dmalloc(&c->d_partials, 2 * kMstepBlocks));
     TRY_OR_FAIL(dmalloc(&c->d_ctrl, 1));
     TRY_OR_FAIL(hipMemsetAsync(c->d_counts, 0, sizeof(double) * ((size_t)M + 1), c->stream));
     TRY_OR_FAIL(hipMemsetAsync(c->d_noise_b, 0, sizeof(double) * c->n_cus * 8, c->stream));
@@ -1642,7 +1400,8 @@ __global__ void k_seed_theta_source(int32_t M, const double* __restrict__ theta,
 // closers: solo_close_round then makes every workgroup one).  Saves one whole E-step launch per rsem_em_run call.
 __global__ __launch_bounds__(kBlock) void k_solo_close(int M, const double* __restrict__ cur, double N0, const Ctrl* ctrl, SoloArgs solo) {
     if (ctrl->done) return;
-    solo_close_round(solo, M, N0, cur);
+    __shared__ CloseScratch close_lds;
+    solo_close_round(solo, M, N0, cur, &close_lds);
 }
 
 // Measured (profiles/r02c_em_loops.log, same box, back to back), ms per round on BASELINE configs[2] / configs[1]:
@@ -1731,6 +1490,12 @@ int rsem_em_run(rsem_em_ctx* c, double* theta, double N0, int round0, int min_ro
         return RSEM_ERR_STATE;
     }
     const size_t R = (size_t)c->M + 1 + 2 * kTotSlots;
+    auto buf = [&](int q) { return c->d_red3 + (size_t)(q % 3) * R; };  // the [counts | totals] buffer round q accumulates into
+    auto lane_io = [&](int q) {  // round q reads theta out of round q-1's buffer
+        LaneIO io;
+        io.theta = buf(q - 1); io.tsrc = buf(q - 1) + c->M + 1; io.N0 = N0; io.counts = buf(q); io.totals = buf(q) + c->M + 1;
+        return io;
+    };
     hipStream_t st2 = c->stream2;
     // SOLO: round r is ONE launch (see SoloArgs); the same three rotating buffers, seeded the same way.  Round q's line and
     // stop decision come out of launch q+1, so the loop issues one launch past max_round (whose own E-step work is unused,
@@ -1739,7 +1504,7 @@ int rsem_em_run(rsem_em_ctx* c, double* theta, double N0, int round0, int min_ro
     if (fused || solo) {
         RSEM_HIP_TRY(hipMemsetAsync(c->d_red3, 0, sizeof(double) * 3 * R, st));
         hipLaunchKernelGGL(k_seed_theta_source, dim3(rsem::ceil_div((uint64_t)c->M + 1 + 2 * kTotSlots, kBlock)), dim3(kBlock), 0, st, c->M,
-                           (const double*)c->d_theta[round0 & 1], N0, c->d_red3 + (size_t)(round0 % 3) * R);
+                           (const double*)c->d_theta[round0 & 1], N0, buf(round0));
         RSEM_HIP_TRY(hipGetLastError());
     }
     int r = round0;
@@ -1751,10 +1516,8 @@ int rsem_em_run(rsem_em_ctx* c, double* theta, double N0, int round0, int min_ro
         int rc = RSEM_OK;
         hipStream_t st_stats = st;  // the stream the round's statistics (and with them the stop flag) are produced on
         if (solo) {
-            double* src = c->d_red3 + (size_t)((r - 1) % 3) * R;
-            double* dst = c->d_red3 + (size_t)(r % 3) * R;
             SoloArgs sa;
-            sa.prev = c->d_red3 + (size_t)((r + 1) % 3) * R;  // = (r - 2) % 3
+            sa.prev = buf(r + 1);  // = round r-2's
             sa.ctrl = c->d_ctrl;
             sa.mirror = mir;
             sa.stat_round = r - 1 > round0 ? r - 1 : 0;
@@ -1763,11 +1526,11 @@ int rsem_em_run(rsem_em_ctx* c, double* theta, double N0, int round0, int min_ro
             if (prof && ti < timed) RSEM_HIP_TRY(hipEventRecord(c->events[2 + 2 * ti], st));
             if (r > max_round) {  // nothing left to accumulate: close round max_round, no E-step work
                 if (c->n_units)
-                    hipLaunchKernelGGL(k_solo_close, dim3(std::min<uint32_t>(c->n_units, (uint32_t)kCloseMax)), dim3(kBlock), 0, st, c->M, (const double*)src, N0,
+                    hipLaunchKernelGGL(k_solo_close, dim3(std::min<uint32_t>(c->n_units, (uint32_t)kCloseMax)), dim3(kBlock), 0, st, c->M, (const double*)buf(r - 1), N0,
                                        (const Ctrl*)c->d_ctrl, sa);
             } else {
-                LaneIO io;
-                io.theta = src; io.tsrc = src + c->M + 1; io.N0 = N0; io.counts = dst; io.totals = dst + c->M + 1; io.solo = sa;
+                LaneIO io = lane_io(r);
+                io.solo = sa;
                 const LanePlan plan = plan_lanes(c, Loop::SOLO);
                 if (plan.fork_join && (rc = fork_x(c, st)) != RSEM_OK) return rc;
                 launch_planned(c, plan, Loop::SOLO, st, io);
@@ -1776,13 +1539,10 @@ int rsem_em_run(rsem_em_ctx* c, double* theta, double N0, int round0, int min_ro
             RSEM_HIP_TRY(hipGetLastError());
             if (prof && ti < timed) RSEM_HIP_TRY(hipEventRecord(c->events[3 + 2 * ti], st));
         } else if (fused) {
-            double* src = c->d_red3 + (size_t)((r - 1) % 3) * R;
-            double* dst = c->d_red3 + (size_t)(r % 3) * R;
+            double* dst = buf(r);
             if (r - round0 >= 3) RSEM_HIP_TRY(hipStreamWaitEvent(st, c->ev_s[(r - 2) & 3], 0));  // dst was cleared by round r-2's statistics
             if (prof && ti < timed) RSEM_HIP_TRY(hipEventRecord(c->events[2 + 2 * ti], st));
-            LaneIO io;
-            io.theta = src; io.tsrc = src + c->M + 1; io.N0 = N0; io.counts = dst; io.totals = dst + c->M + 1;
-            launch_planned(c, plan_lanes(c, Loop::FUSED), Loop::FUSED, st, io);
+            launch_planned(c, plan_lanes(c, Loop::FUSED), Loop::FUSED, st, lane_io(r));
             RSEM_HIP_TRY(hipGetLastError());
             if (prof && ti < timed) RSEM_HIP_TRY(hipEventRecord(c->events[3 + 2 * ti], st));
             if (sharded) {  // EM.cpp:385-389 across shards
@@ -1792,7 +1552,7 @@ int rsem_em_run(rsem_em_ctx* c, double* theta, double N0, int round0, int min_ro
             RSEM_HIP_TRY(hipEventRecord(c->ev_e[r & 3], st));
             RSEM_HIP_TRY(hipStreamWaitEvent(st2, c->ev_e[r & 3], 0));
             hipLaunchKernelGGL(k_mstep_fast<true>, dim3(mstep_fast_grid(c)), dim3(kBlock), 0, st2, c->M, N0, dst, dst + c->M + 1, th_old, th_new,
-                               c->d_counts_last, c->d_ctrl, r, min_round, max_round, mir, src);
+                               c->d_counts_last, c->d_ctrl, r, min_round, max_round, mir, buf(r - 1));
             RSEM_HIP_TRY(hipGetLastError());
             RSEM_HIP_TRY(hipEventRecord(c->ev_s[r & 3], st2));
             st_stats = st2;
@@ -1839,7 +1599,7 @@ int rsem_em_run(rsem_em_ctx* c, double* theta, double N0, int round0, int min_ro
     const int fr = h.final_round;
     if (solo) {  // nothing wrote theta or the final counts on the way: they are in the buffer the stopping round accumulated
         hipLaunchKernelGGL(k_solo_finish, dim3(rsem::ceil_div((uint64_t)c->M + 1, kBlock)), dim3(kBlock), 0, st, c->M, N0,
-                           (const double*)(c->d_red3 + (size_t)(fr % 3) * R), c->d_theta[fr & 1], c->d_counts_last);
+                           (const double*)buf(fr), c->d_theta[fr & 1], c->d_counts_last);
         RSEM_HIP_TRY(hipGetLastError());
     }
     if (fused || solo) RSEM_HIP_TRY(hipMemsetAsync(c->d_red3, 0, sizeof(double) * 3 * R, st));  // leave the shared scratch as the other entry points expect it
@@ -1913,8 +1673,7 @@ int rsem_em_expected_weights(rsem_em_ctx* c, const double* theta, double N0, dou
     // counts: the main E-step kernel (same launch as every theta-only round); weights: their own file-order pass
     int rc = launch_estep(c, c->d_theta[0], c->d_counts, st, nullptr);
     if (rc != RSEM_OK) return rc;
-    hipLaunchKernelGGL(k_mstep_reduce, dim3(kReduceBlocks), dim3(kBlock), 0, st, c->M, N0, c->d_counts, c->d_noise_a, c->noise_n,
-                       c->d_noise_b, n_noise_b(c), c->d_partials, (const Ctrl*)c->d_ctrl);
+    hipLaunchKernelGGL(k_add_noise, dim3(1), dim3(kBlock), 0, st, N0, c->d_counts, c->d_noise_a, c->noise_n, c->d_noise_b, n_noise_b(c));
     RSEM_HIP_TRY(hipGetLastError());
     if ((w || w_noise) && c->N1) {
         rc = launch_weights(c, c->d_theta[0], st);

@@ -42,4 +42,14 @@
    ThreadSanitizer runs report exactly the accesses that are not meant to overlap */
 #define RSEM_STORE_SAME(p, v) (*(p) = (v))
 #define RSEM_NT_LOAD(p) __builtin_nontemporal_load(p)  /* read-once streams: kept out of the way of theta / counts in L2 and MALL */
+/* words that workgroups hand to each other inside a launch (round_close.hpp): relaxed, device scope */
+#define RSEM_AGENT_LOAD(p) __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define RSEM_AGENT_STORE(p, v) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define RSEM_AGENT_EXCHANGE(p, v) __hip_atomic_exchange(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define RSEM_AGENT_FETCH_ADD(p, v) __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define RSEM_AGENT_FETCH_MAX(p, v) __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+/* a word the host polls: everything this thread wrote before it is there for whoever sees it */
+#define RSEM_HOST_RELEASE_STORE(p, v) __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM)
+/* z = 0, computed from x: whatever uses z waits for x to have come back (an ordering by data dependency instead of a fence) */
+#define RSEM_ZERO_DEP(z, x) asm volatile("v_and_b32 %0, 0, %1" : "=v"(z) : "v"(x))
 #endif

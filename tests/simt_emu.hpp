@@ -4,6 +4,7 @@
 // sell_layout.hpp's own index helpers.  Define RSEM_EMU before including.  Never part of the product.
 #pragma once
 #include <pthread.h>
+#include <sched.h>
 
 #include <algorithm>
 #include <atomic>
@@ -18,12 +19,34 @@
 
 // ---- the machine ---------------------------------------------------------------------------------------------------
 namespace emu {
+// The barrier of the machine.  Default: the pthread one (a sleep and a wake-up per lane and barrier).  RSEM_EMU_SPIN_BARRIER (defined
+// before this header by an emulator whose kernel is mostly barriers, tests/round_close_emu.cpp): one that spins and yields.
+#ifdef RSEM_EMU_SPIN_BARRIER
+struct Barrier {
+    std::atomic<int> arrived{0}, phase{0};
+    int n = 0;
+};
+inline void barrier_init(Barrier* b, int n) { b->n = n; }
+inline void barrier_wait(Barrier* b) {
+    const int ph = b->phase.load(std::memory_order_acquire);
+    if (b->arrived.fetch_add(1, std::memory_order_acq_rel) == b->n - 1) {
+        b->arrived.store(0, std::memory_order_relaxed);
+        b->phase.store(ph + 1, std::memory_order_release);
+        return;
+    }
+    while (b->phase.load(std::memory_order_acquire) == ph) sched_yield();
+}
+#else
+using Barrier = pthread_barrier_t;
+inline void barrier_init(Barrier* b, int n) { pthread_barrier_init(b, nullptr, n); }
+inline void barrier_wait(Barrier* b) { pthread_barrier_wait(b); }
+#endif
 struct Wave {
-    pthread_barrier_t bar;
+    Barrier bar;
     unsigned long long slot[64];
 };
 struct Block {
-    pthread_barrier_t bar;
+    Barrier bar;
     Wave w[4];
 };
 thread_local int t_tid = 0;
@@ -37,9 +60,9 @@ inline T exchange(T v, int src) {  // every lane of the wave calls this; returns
     unsigned long long raw = 0;
     memcpy(&raw, &v, sizeof(T));
     w.slot[lane()] = raw;
-    pthread_barrier_wait(&w.bar);
+    barrier_wait(&w.bar);
     if (src >= 0 && src < 64) raw = w.slot[src];
-    pthread_barrier_wait(&w.bar);
+    barrier_wait(&w.bar);
     T r;
     memcpy(&r, &raw, sizeof(T));
     return r;
@@ -47,10 +70,10 @@ inline T exchange(T v, int src) {  // every lane of the wave calls this; returns
 inline unsigned long long ballot(bool p) {
     Wave& w = wave();
     w.slot[lane()] = p ? 1ull : 0ull;
-    pthread_barrier_wait(&w.bar);
+    barrier_wait(&w.bar);
     unsigned long long m = 0;
     for (int i = 0; i < 64; i++) m |= w.slot[i] << i;
-    pthread_barrier_wait(&w.bar);
+    barrier_wait(&w.bar);
     return m;
 }
 inline int dpp_src(int ctrl) {
@@ -82,6 +105,18 @@ inline void store_same(double* p, double v) {
     memcpy(&u, &v, 8);
     reinterpret_cast<std::atomic<unsigned long long>*>(p)->store(u, std::memory_order_relaxed);
 }
+// the words workgroups hand to each other (round_close.hpp): relaxed atomics
+template <typename T>
+inline T a_load(T* p) { T r; __atomic_load(p, &r, __ATOMIC_RELAXED); return r; }
+template <typename T, typename V>
+inline void a_store(T* p, V v, int order) { T t = (T)v; __atomic_store(p, &t, order); }
+template <typename T>
+inline T a_exchange(T* p, T v) { T r; __atomic_exchange(p, &v, &r, __ATOMIC_RELAXED); return r; }
+inline unsigned long long a_fetch_max(unsigned long long* p, unsigned long long v) {
+    unsigned long long old = __atomic_load_n(p, __ATOMIC_RELAXED);
+    while (old < v && !__atomic_compare_exchange_n(p, &old, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+    return old;
+}
 inline double ll_as_double(long long x) { double d; memcpy(&d, &x, 8); return d; }
 inline long long double_as_ll(double d) { long long x; memcpy(&x, &d, 8); return x; }
 }  // namespace emu
@@ -89,7 +124,7 @@ inline long long double_as_ll(double d) { long long x; memcpy(&x, &d, 8); return
 #define RSEM_DEVFN inline
 #define RSEM_TIDX (emu::t_tid)
 #define RSEM_BDIM 256
-#define RSEM_SYNC() pthread_barrier_wait(&emu::t_blk->bar)
+#define RSEM_SYNC() emu::barrier_wait(&emu::t_blk->bar)
 #define RSEM_SHFL_XOR(v, d) emu::exchange(v, emu::lane() ^ (d))
 #define RSEM_SHFL_DOWN(v, d) emu::exchange(v, emu::lane() + (d))
 #define RSEM_SHFL_UP(v, d) emu::exchange(v, emu::lane() - (d))
@@ -101,7 +136,7 @@ inline long long double_as_ll(double d) { long long x; memcpy(&x, &d, 8); return
 #define RSEM_LDS_ADD(p, v) emu::atomic_add(p, v)
 #define RSEM_LDS_ADD_I32(p, v) __atomic_fetch_add(p, v, __ATOMIC_RELAXED)
 #define RSEM_LDS_FETCH_ADD_I32(p, v) __atomic_fetch_add(p, v, __ATOMIC_RELAXED)
-#define RSEM_WAVE_SYNC() pthread_barrier_wait(&emu::wave().bar)
+#define RSEM_WAVE_SYNC() emu::barrier_wait(&emu::wave().bar)
 #define RSEM_WAIT_VM0() __atomic_thread_fence(__ATOMIC_SEQ_CST)
 #define RSEM_READFIRSTLANE(v) emu::exchange(v, 0)
 #define RSEM_PIN(x) (void)(x)
@@ -112,6 +147,13 @@ inline long long double_as_ll(double d) { long long x; memcpy(&x, &d, 8); return
 #define RSEM_DOUBLE_AS_LL(x) emu::double_as_ll(x)
 #define RSEM_NT_LOAD(p) (*(p))
 #define RSEM_STORE_SAME(p, v) emu::store_same(p, v)
+#define RSEM_AGENT_LOAD(p) emu::a_load(p)
+#define RSEM_AGENT_STORE(p, v) emu::a_store(p, v, __ATOMIC_RELAXED)
+#define RSEM_AGENT_EXCHANGE(p, v) emu::a_exchange(p, v)
+#define RSEM_AGENT_FETCH_ADD(p, v) __atomic_fetch_add(p, v, __ATOMIC_RELAXED)
+#define RSEM_AGENT_FETCH_MAX(p, v) emu::a_fetch_max(p, v)
+#define RSEM_HOST_RELEASE_STORE(p, v) emu::a_store(p, v, __ATOMIC_RELEASE)
+#define RSEM_ZERO_DEP(z, x) ((void)(x), __atomic_thread_fence(__ATOMIC_SEQ_CST), (z) = 0)
 
 // ---- the layout, on the host -----------------------------------------------------------------------------------------
 struct HostLayout {
