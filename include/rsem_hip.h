@@ -268,6 +268,15 @@ int rsem_model_round(rsem_model_ctx* ctx, const double* theta, double N0, double
                      double* sum, double* bChange, int32_t* totNum, rsem_model_accum* acc /* NULL: no statistics */);
 /* current CSR values back to the host in file order (for imd.ofg, EM.cpp:421-457) */
 int rsem_model_get_values(rsem_model_ctx* ctx, double* conprb, double* ncp);
+/* Facts of a model context:
+ *   "window_addr_bits"  the width of the per-alignment addresses into the array of transcript strands: 32 while both strands of
+ *                       every transcript (each rounded up to 8 bytes) + 16 bytes stay below 2^32, else 40.  References beyond
+ *                       2^40 bytes are refused by rsem_model_create (RSEM_ERR_INVALID), before anything is uploaded;
+ *   "strand_bytes"      both strands of every transcript, each rounded up to 8 bytes;
+ *   "strand_pad_bytes"  the environment variable RSEM_MODEL_STRAND_PAD, read by rsem_model_create (a whole number of bytes, a
+ *                       multiple of 8; anything else makes the create fail with RSEM_ERR_INVALID): device bytes allocated in front
+ *                       of the strands, never written or read, counted in every address (a test knob: small inputs above 2^32). */
+int rsem_model_get_info(const rsem_model_ctx* ctx, const char* key, int64_t* value);
 int rsem_model_destroy(rsem_model_ctx* ctx);
 
 /* ------------------------------------------------------------------------------------------

@@ -556,6 +556,12 @@ int main(int argc, char* argv[]) {
         if (X.rc != RSEM_OK) X.err = rsem_hip_last_error();
     });
     check_shards("rsem_model_create");
+    for (int k = 0; k < S; k++) {  // references of 4 GiB of strands and more: said once per shard, nothing new otherwise
+        int64_t bits = 32, bytes = 0;
+        if (rsem_model_get_info(sh[k].mc, "window_addr_bits", &bits) != RSEM_OK || rsem_model_get_info(sh[k].mc, "strand_bytes", &bytes) != RSEM_OK)
+            die("rsem-run-em: rsem_model_get_info failed on shard %d: %s", k, rsem_hip_last_error());
+        if (bits > 32 && verbose) printf("model: window addresses of %lld bits (strands %lld bytes)\n", (long long)bits, (long long)bytes);
+    }
     mark("model contexts built (reads, references, alignment fields uploaded)");
     if (getenv("RSEM_HIP_TIMING") && atoi(getenv("RSEM_HIP_TIMING")) >= 2) {
         int64_t b = 0, ns = 0, nf = 0, nw = 0;

@@ -79,14 +79,18 @@ __global__ __launch_bounds__(kBlk) void k_window_flags(DevData D, uint8_t* flags
 
 // DevData::aw0 .. atot and bit 2 of the flags (model_block.hpp alignment_fields): one thread per alignment, once per model context
 // and seed length.  Low-quality reads are never walked (and their coordinates were not range-checked): zeros.
-template <bool kPE>
-__global__ __launch_bounds__(kBlk) void k_alignment_fields(DevData D, int seedLen, uint32_t* aw0, uint32_t* aw1, uint32_t* afull, uint32_t* atot, uint8_t* flags) {
+// kWide: + the addresses' bits 32..39 (aw0h / aw1h; not touched otherwise).
+template <bool kPE, bool kWide = false>
+__global__ __launch_bounds__(kBlk) void k_alignment_fields(DevData D, int seedLen, uint32_t* aw0, uint32_t* aw1, uint32_t* afull, uint32_t* atot, uint8_t* flags,
+                                                           uint8_t* aw0h = nullptr, uint8_t* aw1h = nullptr) {
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= D.nnz) return;
     AlnFields F{0u, 0u, 1u, 1u, false};
-    if (!D.lq[D.hit_row[j]]) F = alignment_fields<kPE>(D, seedLen, j);
+    if (!D.lq[D.hit_row[j]]) F = alignment_fields<kPE, kWide>(D, seedLen, j);
     aw0[j] = F.a0;
     if (kPE) aw1[j] = F.a1;
+    if (kWide) aw0h[j] = F.h0;
+    if (kWide && kPE) aw1h[j] = F.h1;
     afull[j] = F.full;
     atot[j] = F.tot;
     flags[j] = (uint8_t)((flags[j] & 3u) | (F.masked ? 4u : 0u));
@@ -108,7 +112,7 @@ static_assert(kGroupBlk / 64 * 4 == 32 && (kGroupChunk == 0 || (kGroupChunk > 0 
 #ifndef RSEM_GROUP_ATTR
 #define RSEM_GROUP_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
 #endif
-template <bool kQ, bool kPE, bool kUpdate>
+template <bool kQ, bool kPE, bool kUpdate, bool kWide = false>
 __global__ __launch_bounds__(kGroupBlk) RSEM_GROUP_ATTR void k_model_group(DevData D, DevTables T, const double* __restrict__ theta, double* __restrict__ cp,
                                                              double* __restrict__ ncp, AccumPtrs A, PlaneOut PO) {
     __shared__ double s_prob[kQ ? kQProbLds : 1];            // QProfile (100 x 5 x 5) + the pad code's entries; the position-indexed Profile stays in global memory
@@ -137,10 +141,10 @@ __global__ __launch_bounds__(kGroupBlk) RSEM_GROUP_ATTR void k_model_group(DevDa
     // chunks of kGroupChunk rows dealt to the workgroups round-robin; inside a chunk the workgroup's waves take 4 rows each per step
     const uint64_t waves_per_block = blockDim.x / 64;
     if (kGroupChunk > 0)
-        model_group_rows<kQ, kPE, kUpdate>(D, T, theta, cp, ncp, A, kQ ? s_prob : T.prof, s_nprob, s_prof, s_noise, s_rspd, s_gld, (uint64_t)(threadIdx.x >> 6) * 4,
+        model_group_rows<kQ, kPE, kUpdate, kWide>(D, T, theta, cp, ncp, A, kQ ? s_prob : T.prof, s_nprob, s_prof, s_noise, s_rspd, s_gld, (uint64_t)(threadIdx.x >> 6) * 4,
                                            waves_per_block * 4, lane, PO, (uint64_t)kGroupChunk, (uint64_t)blockIdx.x, (uint64_t)gridDim.x);
     else  // (measurement builds, -DRSEM_GROUP_CHUNK=0: the grid-wide stride of rounds 4-5)
-        model_group_rows<kQ, kPE, kUpdate>(D, T, theta, cp, ncp, A, kQ ? s_prob : T.prof, s_nprob, s_prof, s_noise, s_rspd, s_gld,
+        model_group_rows<kQ, kPE, kUpdate, kWide>(D, T, theta, cp, ncp, A, kQ ? s_prob : T.prof, s_nprob, s_prof, s_noise, s_rspd, s_gld,
                                            ((uint64_t)blockIdx.x * waves_per_block + (threadIdx.x >> 6)) * 4, (uint64_t)gridDim.x * waves_per_block * 4, lane, PO);
     if (!kUpdate) return;
     __syncthreads();
@@ -242,6 +246,9 @@ struct rsem_model_ctx {
     int B_alloc = 0, gld_n = 0, mld_n = 0, prof_n = 0, noise_n = 0;
     std::vector<void*> owned;       // device allocations of the immutable data
     uint32_t *d_aw0 = nullptr, *d_aw1 = nullptr, *d_afull = nullptr, *d_atot = nullptr;  // DevData::aw0 .. atot (owned)
+    uint8_t *d_aw0h = nullptr, *d_aw1h = nullptr;  // DevData::aw0h / aw1h (owned; the wide path only)
+    int addr_bits = 32;             // window_addr_bits of this context: 32 = the narrow instantiations, else the wide ones
+    uint64_t strand_bytes = 0, strand_pad = 0;  // both strands of every transcript; RSEM_MODEL_STRAND_PAD
     uint8_t* d_flags = nullptr;     // DevData::same_prev, writable (bit 2 is set with the first tables: it needs the seed length)
     int fields_seedLen = -1;        // the seed length aw0 .. atot / bit 2 were computed with (-1: not yet)
     double* d_theta = nullptr;                // the round's theta for the weights of k_model_group, [M+1]
@@ -269,7 +276,7 @@ int up_field(rsem_model_ctx* c, const T*& field, const T* src, size_t n, hipStre
 // the group-per-read kernel: conprb + noise (+ weights and statistics when theta / accumulators are given).  (The thread-per-
 // alignment and thread-per-read kernel families of rounds 2-3, kept behind RSEM_MODEL_KERNELS as cross-checks until round 5, left the
 // product in round 6: the kernel body is checked on the CPU emulator and the programs against the reference's files.)
-template <bool kQ, bool kPE>
+template <bool kQ, bool kPE, bool kWide>
 int launch_group(rsem_model_ctx* c, const double* d_theta, const AccumPtrs* A, const PlaneOut& PO) {
     if (!c->D.N1) return RSEM_OK;
     if (!c->n_cus) {
@@ -280,9 +287,9 @@ int launch_group(rsem_model_ctx* c, const double* d_theta, const AccumPtrs* A, c
     const uint64_t chunks = kGroupChunk > 0 ? (c->D.N1 + kGroupChunk - 1) / kGroupChunk : (c->D.N1 + 31) / 32;
     const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->n_cus * 2, chunks));
     if (A)
-        hipLaunchKernelGGL((k_model_group<kQ, kPE, true>), dim3(grid), dim3(kGroupBlk), 0, c->v.stream, c->D, c->T, d_theta, c->v.d_cp, c->v.d_ncp, *A, PO);
+        hipLaunchKernelGGL((k_model_group<kQ, kPE, true, kWide>), dim3(grid), dim3(kGroupBlk), 0, c->v.stream, c->D, c->T, d_theta, c->v.d_cp, c->v.d_ncp, *A, PO);
     else
-        hipLaunchKernelGGL((k_model_group<kQ, kPE, false>), dim3(grid), dim3(kGroupBlk), 0, c->v.stream, c->D, c->T, (const double*)nullptr, c->v.d_cp,
+        hipLaunchKernelGGL((k_model_group<kQ, kPE, false, kWide>), dim3(grid), dim3(kGroupBlk), 0, c->v.stream, c->D, c->T, (const double*)nullptr, c->v.d_cp,
                            c->v.d_ncp, AccumPtrs{nullptr, nullptr, nullptr, nullptr, 0, 0}, PO);
     RSEM_HIP_TRY(hipGetLastError());
     return RSEM_OK;
@@ -304,12 +311,21 @@ int launch_group_any(rsem_model_ctx* c, const double* d_theta, const AccumPtrs* 
     }
     if (in_place) PO = PlaneOut{pv.d_rank, (const Shape*)pv.d_shapes, pv.n_shapes, pv.T, pv.n_sell_rows, pv.d_sval, pv.d_sncp};
     int rc;
-    switch (c->D.model_type) {
-        case 0: rc = launch_group<false, false>(c, d_theta, A, PO); break;
-        case 1: rc = launch_group<true, false>(c, d_theta, A, PO); break;
-        case 2: rc = launch_group<false, true>(c, d_theta, A, PO); break;
-        default: rc = launch_group<true, true>(c, d_theta, A, PO); break;
-    }
+    // (the instantiation was chosen once, at create: window_addr_bits)
+    if (c->addr_bits == 32)
+        switch (c->D.model_type) {
+            case 0: rc = launch_group<false, false, false>(c, d_theta, A, PO); break;
+            case 1: rc = launch_group<true, false, false>(c, d_theta, A, PO); break;
+            case 2: rc = launch_group<false, true, false>(c, d_theta, A, PO); break;
+            default: rc = launch_group<true, true, false>(c, d_theta, A, PO); break;
+        }
+    else
+        switch (c->D.model_type) {
+            case 0: rc = launch_group<false, false, true>(c, d_theta, A, PO); break;
+            case 1: rc = launch_group<true, false, true>(c, d_theta, A, PO); break;
+            case 2: rc = launch_group<false, true, true>(c, d_theta, A, PO); break;
+            default: rc = launch_group<true, true, true>(c, d_theta, A, PO); break;
+        }
     if (rc != RSEM_OK) return rc;
     return in_place ? rsem::em_values_written_in_place(c->em) : rsem::em_values_changed(c->em);
 }
@@ -332,7 +348,7 @@ int rsem_model_destroy(rsem_model_ctx* c) {
     (void)hipSetDevice(c->v.device);
     if (c->em && c->holds_view) rsem::em_view_release(c->em);
     for (void* p : c->owned) hipFree(p);
-    hipFree(c->d_aw0); hipFree(c->d_aw1); hipFree(c->d_afull); hipFree(c->d_atot);
+    hipFree(c->d_aw0); hipFree(c->d_aw1); hipFree(c->d_afull); hipFree(c->d_atot); hipFree(c->d_aw0h); hipFree(c->d_aw1h);
     hipFree(c->t_rspd_pdf); hipFree(c->t_rspd_cdf); hipFree(c->t_gld_pdf); hipFree(c->t_gld_cdf); hipFree(c->t_mld_pdf);
     hipFree(c->t_mld_cdf); hipFree(c->t_prof); hipFree(c->t_noise); hipFree(c->t_mw);
     hipFree(c->a_prof); hipFree(c->a_noise); hipFree(c->a_rspd); hipFree(c->a_gld);
@@ -351,9 +367,32 @@ int rsem_model_create(rsem_model_ctx** out, rsem_em_ctx* em, const rsem_model_da
                  "NULL array in rsem_model_data");
     RSEM_REQUIRE(!pe || (d->insertL && d->read_off[1] && d->read_seq[1]), "paired-end data needs insertL and mate 2");
     RSEM_REQUIRE(!q || (d->read_qual[0] && (!pe || d->read_qual[1])), "quality models need read_qual");
+    // How the strand array will be addressed (window_addr_bits), decided before anything is built or uploaded.
+    // RSEM_MODEL_STRAND_PAD (a test seam): that many bytes in front of the strands on the device -- allocated,
+    // never written, never read -- so that kilobytes of input have window addresses above 2^32.
+    uint64_t strand_pad = 0, strand_bytes = 0;
+    if (const char* e = getenv("RSEM_MODEL_STRAND_PAD")) {
+        char* end = nullptr;
+        const unsigned long long v = strtoull(e, &end, 10);
+        RSEM_REQUIRE(end != e && *end == '\0' && e[0] >= '0' && e[0] <= '9' && v % 8 == 0, "RSEM_MODEL_STRAND_PAD must be a whole number of bytes, a multiple of 8");
+        strand_pad = v;
+    }
+    for (int sid = 1; sid <= d->M; sid++) {
+        RSEM_REQUIRE(d->totLen[sid] >= 0, "negative transcript length");
+        strand_bytes += 2 * (((uint64_t)d->totLen[sid] + 7) / 8 * 8);
+    }
+    const int addr_bits = window_addr_bits(strand_bytes, strand_pad);
+    if (!addr_bits) {
+        rsem::set_last_error("the transcript sequences take %llu bytes on both strands (+ %llu bytes of RSEM_MODEL_STRAND_PAD): the model context addresses them with at most %d bits",
+                             (unsigned long long)strand_bytes, (unsigned long long)strand_pad, kWideAddrBits);
+        return RSEM_ERR_INVALID;
+    }
     rsem_model_ctx* c = new (std::nothrow) rsem_model_ctx();
     if (!c) return RSEM_ERR_NOMEM;
     c->em = em;
+    c->addr_bits = addr_bits;
+    c->strand_bytes = strand_bytes;
+    c->strand_pad = strand_pad;
     int rc = rsem::em_device_view(em, &c->v);
     if (rc != RSEM_OK) { delete c; return rc; }
     rsem::em_view_hold(em);
@@ -457,11 +496,16 @@ int rsem_model_create(rsem_model_ctx** out, rsem_em_ctx* em, const rsem_model_da
     UP(lq, d->low_quality, d->N1);
     {   // both strands of every transcript (built beside the uploads above: strand_builder)
         strand_builder.join();
-        UP(soff, soff.data(), soff.size());
-        const uint64_t* wptr = nullptr;
-        rc = up_field(c, wptr, reinterpret_cast<const uint64_t*>(strands.data()), (tot + 16) / 8, st);
+        // (the device's offsets and every window address count from the start of the allocation: the pad lies in front)
+        std::vector<uint64_t> soff_dev(soff);
+        for (int sid = 1; sid <= d->M; sid++) { soff_dev[2 * sid] += strand_pad; soff_dev[2 * sid + 1] += strand_pad; }
+        UP(soff, soff_dev.data(), soff_dev.size());
+        uint8_t* wptr = nullptr;
+        if (dmalloc(&wptr, (size_t)(strand_pad + tot + 16)) != hipSuccess) { rsem_model_destroy(c); return RSEM_ERR_NOMEM; }
+        c->owned.push_back(wptr);
+        rc = rsem::staged_h2d(wptr + strand_pad, strands.data(), (size_t)(tot + 16), st);
         if (rc != RSEM_OK) { rsem_model_destroy(c); return rc; }
-        D.refw = wptr;
+        D.refw = reinterpret_cast<const uint64_t*>(wptr);
         if (hipStreamSynchronize(st) != hipSuccess) { rsem_model_destroy(c); return RSEM_ERR_HIP; }
     }
     UP(fullLen, d->fullLen, (size_t)d->M + 1);
@@ -479,17 +523,12 @@ int rsem_model_create(rsem_model_ctx** out, rsem_em_ctx* em, const rsem_model_da
     c->owned.push_back(fl);
     D.same_prev = fl;
     c->d_flags = fl;
-    {   // the strand array is addressed with 32 bits per alignment (DevData::aw0 / aw1)
-        uint64_t strand_bytes = 0;
-        for (int sid = 1; sid <= d->M; sid++) strand_bytes += 2 * (((uint64_t)d->totLen[sid] + 7) / 8 * 8);
-        if (strand_bytes + 16 >= (1ull << 32)) {
-            rsem_model_destroy(c);
-            rsem::set_last_error("the transcript sequences take %llu bytes on both strands: the model context addresses them with 32 bits", (unsigned long long)strand_bytes);
-            return RSEM_ERR_INVALID;
-        }
+    {   // the strand array is addressed with 32 bits per alignment (DevData::aw0 / aw1), on the wide path with a byte more each
+        const bool wide = c->addr_bits != 32;
         if (dmalloc(&c->d_aw0, d->nnz) != hipSuccess || (pe && dmalloc(&c->d_aw1, d->nnz) != hipSuccess) || dmalloc(&c->d_afull, d->nnz) != hipSuccess ||
-            dmalloc(&c->d_atot, d->nnz) != hipSuccess) { rsem_model_destroy(c); return RSEM_ERR_NOMEM; }
-        D.aw0 = c->d_aw0; D.aw1 = c->d_aw1; D.afull = c->d_afull; D.atot = c->d_atot;
+            dmalloc(&c->d_atot, d->nnz) != hipSuccess || (wide && dmalloc(&c->d_aw0h, d->nnz) != hipSuccess) ||
+            (wide && pe && dmalloc(&c->d_aw1h, d->nnz) != hipSuccess)) { rsem_model_destroy(c); return RSEM_ERR_NOMEM; }
+        D.aw0 = c->d_aw0; D.aw1 = c->d_aw1; D.afull = c->d_afull; D.atot = c->d_atot; D.aw0h = c->d_aw0h; D.aw1h = c->d_aw1h;
     }
     if (d->nnz) {
         if (pe) hipLaunchKernelGGL(k_window_flags<true>, dim3(rsem::ceil_div(d->nnz, kBlk)), dim3(kBlk), 0, st, D, fl);
@@ -542,9 +581,14 @@ int rsem_model_set_tables(rsem_model_ctx* c, const rsem_model_tables* t) {
     T.prof_rows = t->prof_rows; T.prof = c->t_prof; T.noise = c->t_noise; T.mw = c->t_mw;
     if (c->fields_seedLen != t->seedLen) {  // (once per context in the programs: the seed length is a constant of the model)
         if (c->D.nnz) {
-            const bool pe = c->D.model_type >= 2;
-            if (pe) hipLaunchKernelGGL(k_alignment_fields<true>, dim3(rsem::ceil_div(c->D.nnz, kBlk)), dim3(kBlk), 0, st, c->D, t->seedLen, c->d_aw0, c->d_aw1, c->d_afull, c->d_atot, c->d_flags);
-            else hipLaunchKernelGGL(k_alignment_fields<false>, dim3(rsem::ceil_div(c->D.nnz, kBlk)), dim3(kBlk), 0, st, c->D, t->seedLen, c->d_aw0, c->d_aw1, c->d_afull, c->d_atot, c->d_flags);
+            const bool pe = c->D.model_type >= 2, wide = c->addr_bits != 32;
+            const dim3 grid(rsem::ceil_div(c->D.nnz, kBlk));
+#define FIELDS(PE, WIDE)                                                                                                                                  \
+    hipLaunchKernelGGL((k_alignment_fields<PE, WIDE>), grid, dim3(kBlk), 0, st, c->D, t->seedLen, c->d_aw0, c->d_aw1, c->d_afull, c->d_atot, c->d_flags, \
+                       c->d_aw0h, c->d_aw1h)
+            if (!wide) { if (pe) FIELDS(true, false); else FIELDS(false, false); }
+            else { if (pe) FIELDS(true, true); else FIELDS(false, true); }
+#undef FIELDS
             RSEM_HIP_TRY(hipGetLastError());
             RSEM_HIP_TRY(hipStreamSynchronize(st));
         }
@@ -612,6 +656,15 @@ int rsem_model_round(rsem_model_ctx* c, const double* theta, double N0, double* 
         if (pe) RSEM_HIP_TRY(hipMemcpyAsync(acc->gld, c->a_gld, sizeof(double) * ng, hipMemcpyDeviceToHost, st));
         RSEM_HIP_TRY(hipStreamSynchronize(st));
     }
+    return RSEM_OK;
+}
+
+int rsem_model_get_info(const rsem_model_ctx* c, const char* key, int64_t* value) {
+    RSEM_REQUIRE(c && key && value, "NULL argument");
+    if (!strcmp(key, "window_addr_bits")) *value = c->addr_bits;
+    else if (!strcmp(key, "strand_bytes")) *value = (int64_t)c->strand_bytes;
+    else if (!strcmp(key, "strand_pad_bytes")) *value = (int64_t)c->strand_pad;
+    else { rsem::set_last_error("unknown info key '%s'", key); return RSEM_ERR_INVALID; }
     return RSEM_OK;
 }
 

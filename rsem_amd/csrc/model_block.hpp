@@ -95,7 +95,22 @@ struct DevData {
     const uint32_t* aw1;     // [nnz] window of mate 2 (paired-end only)
     const uint32_t* afull;   // [nnz] fullLen of the transcript
     const uint32_t* atot;    // [nnz] totLen of the transcript
+    // strand arrays of 4 GiB and more (kWide instantiations only, else nullptr): bits 32..39 of the two window addresses, a byte
+    // each -- aw0 / aw1 stay the low words, afull / atot and the position fields keep all their bits
+    const uint8_t* aw0h;     // [nnz]
+    const uint8_t* aw1h;     // [nnz] (paired-end only)
 };
+
+// How a model context addresses its strand array: `strand_bytes` = both strands of every transcript, each rounded up to 8 bytes;
+// `pad` = the bytes allocated in front of them (RSEM_MODEL_STRAND_PAD, a test seam: 0 in the product).  The array ends in two
+// spare words (the 8-byte fetches of the last window look one word ahead).  -> 32: DevData::aw0 / aw1 alone (every context before
+// the wide path existed is here, and stays here); 40: with the high bytes aw0h / aw1h; 0: refused.
+constexpr int kWideAddrBits = 40;
+constexpr int window_addr_bits(uint64_t strand_bytes, uint64_t pad) {
+    if (strand_bytes >= (1ull << kWideAddrBits) || pad >= (1ull << kWideAddrBits)) return 0;  // (no sum below wraps)
+    const uint64_t end = strand_bytes + pad + 16;
+    return end < (1ull << 32) ? 32 : end < (1ull << kWideAddrBits) ? kWideAddrBits : 0;
+}
 
 // Where the sliced layout of the EM context (sell_layout.hpp) keeps the values of a read: with this the round kernel writes
 // every alignment probability straight into its value plane (and the noise probability into its row slot) instead of
@@ -154,8 +169,9 @@ RSEM_DEVFN bool ref_mask(const DevData& D, int sid, int p) {  // RefSeq.h:89-92
 // The per-alignment fields above, from the per-transcript tables (alignment j of a read that is not low-quality; seedLen: the
 // model's, SingleQModel.h:108-110).  `masked` = what getConPrb asks RefSeq::getMask for this alignment (SingleModel.h:104-106,
 // PairedEndModel.h:100-102); the position is range-checked here, the kernel's own test `pos >= fullLen` comes first there too.
-struct AlnFields { uint32_t a0, a1, full, tot; bool masked; };
-template <bool kPE>
+// kWide: h0 / h1 = bits 32..39 of the window addresses (DevData::aw0h / aw1h), 0 otherwise.
+struct AlnFields { uint32_t a0, a1, full, tot; bool masked; uint8_t h0, h1; };
+template <bool kPE, bool kWide = false>
 RSEM_DEVFN AlnFields alignment_fields(const DevData& D, int seedLen, uint64_t j) {
     AlnFields F;
     const int s = D.sid_signed[j];
@@ -166,6 +182,8 @@ RSEM_DEVFN AlnFields alignment_fields(const DevData& D, int seedLen, uint64_t j)
     F.tot = (uint32_t)tot;
     F.a0 = (uint32_t)(D.soff[2 * sid + dir] + (uint64_t)pos);
     F.a1 = kPE ? (uint32_t)(D.soff[2 * sid + (dir ^ 1)] + (uint64_t)(tot - pos - ins)) : 0u;
+    F.h0 = kWide ? (uint8_t)((D.soff[2 * sid + dir] + (uint64_t)pos) >> 32) : (uint8_t)0;
+    F.h1 = (kWide && kPE) ? (uint8_t)((D.soff[2 * sid + (dir ^ 1)] + (uint64_t)(tot - pos - ins)) >> 32) : (uint8_t)0;
     const int p = kPE ? (dir == 0 ? pos : tot - pos - ins) : (dir == 0 ? pos : tot - pos - seedLen);
     F.masked = (p >= 0 && p < full) ? ref_mask(D, sid, p) : false;
     return F;
@@ -400,7 +418,9 @@ RSEM_DEVFN double alignment_prob(const DevData& D, const DevTables& T, const Chu
 // XCD (the grid-wide stride of rounds 4-5 fetched 4.2 x the bytes the kernel uses: profiles/r06b_model_group_pmc.json).
 // prob / nprob: the profile / noise probability tables (LDS copies where they fit); s_*: the LDS count tables of the update.
 // theta (kUpdate): the round's theta, for the posterior weights.  cp / ncp: the CSR values, written for every read.
-template <bool kQ, bool kPE, bool kUpdate>
+// kWide: the window addresses take their bits 32..39 from DevData::aw0h / aw1h (strand arrays of 4 GiB and more, window_addr_bits);
+// everything behind load_chunk holds them in 64 bits either way.
+template <bool kQ, bool kPE, bool kUpdate, bool kWide = false>
 RSEM_DEVFN void model_group_rows(const DevData& D, const DevTables& T, const double* __restrict__ theta, double* __restrict__ cp,
                                  double* __restrict__ ncp, const AccumPtrs& A, const double* prob, const double* nprob, double* s_prof,
                                  double* s_noise, double* s_rspd, double* s_gld, uint64_t row0, uint64_t row_stride, int lane,
@@ -499,6 +519,8 @@ RSEM_DEVFN void model_group_rows(const DevData& D, const DevTables& T, const dou
             const int s_v = D.sid_signed[j], pos_v = D.pos[j], ins_v = kPE ? D.insertL[j] : 0;
             const unsigned fl_v = D.same_prev[j];
             const uint32_t a0_v = D.aw0[j], a1_v = kPE ? D.aw1[j] : 0u, full_v = D.afull[j], tot_v = D.atot[j];
+            // (kWide: two more loads of the same round trip, for the same stand-in index, masked below like the others)
+            const uint32_t a0h_v = kWide ? D.aw0h[j] : 0u, a1h_v = (kWide && kPE) ? D.aw1h[j] : 0u;
             const int s = R.has ? s_v : 1;
             R.sid = s < 0 ? -s : s;
             R.dir = s < 0 ? 1 : 0;
@@ -507,8 +529,13 @@ RSEM_DEVFN void model_group_rows(const DevData& D, const DevTables& T, const dou
             R.flags = R.has ? fl_v : 0u;
             R.fullLen = R.has ? (int)full_v : 1;
             R.totLen = R.has ? (int)tot_v : 1;
-            R.a[0] = R.has ? (uint64_t)a0_v : 0;
-            if (kPE) R.a[kMates - 1] = R.has ? (uint64_t)a1_v : 0;
+            if (!kWide) {
+                R.a[0] = R.has ? (uint64_t)a0_v : 0;
+                if (kPE) R.a[kMates - 1] = R.has ? (uint64_t)a1_v : 0;
+            } else {
+                R.a[0] = R.has ? (((uint64_t)a0h_v << 32) | (uint64_t)a0_v) : 0;
+                if (kPE) R.a[kMates - 1] = R.has ? (((uint64_t)a1h_v << 32) | (uint64_t)a1_v) : 0;
+            }
             R.cp = 0.0;
             if (in && !R.has) { cp[j] = 0.0; plane_put(idx, 0.0); }  // low-quality read: every alignment gets probability 0 (SingleQModel.h:102)
         };
