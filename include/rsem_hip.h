@@ -349,6 +349,29 @@ int rsem_gibbs_destroy(rsem_gibbs_ctx* ctx);
 /* sampling.h:19-44: seeds of the first nchains chains for --seed seed. */
 int rsem_gibbs_chain_seeds(uint32_t seed, int nchains, uint32_t* out);
 
+/* Convergence diagnostics of a run's count vectors (no counterpart in the reference, which writes the vectors, Gibbs.cpp:257-262,
+ * and says nothing about whether its chains agree).  count_vectors: nchains host pointers, block k =
+ * nsamples[k] x (M+1) int32 as rsem_gibbs_run_chains returns them = the lines of imd.countvectors<k>.  Every chain gives its LAST
+ * n' = 2 * (min_k nsamples[k] / 2) rows, cut in two: m = 2 * nchains sequences of n = n' / 2 values per transcript.  Per transcript
+ * 0 .. M: mean, sd = sqrt(var+), split-R-hat = sqrt(var+ / W), the effective sample size m n / tau with tau from Geyer's initial
+ * monotone sequence over the autocorrelations (held at 1 / log10(m n) from below) and the last lag that sum took.  W = 0 gives
+ * rhat = +inf (the sequences' means differ) or NaN (they do not), ess = NaN, lag = 0.  Needs no context; n < 2, NULL or negative
+ * arguments: RSEM_ERR_INVALID; vectors that do not fit the device's free memory: RSEM_ERR_NOMEM, nothing attempted.
+ * The environment variable RSEM_GIBBS_DIAG_L0 (odd, 1 .. 63; anything else: RSEM_ERR_INVALID), read at call time, sets the lag up
+ * to which the first kernel decides a transcript (a test / measurement knob: the results do not depend on it, n_long does). */
+typedef struct {
+    int32_t n_used, sequences;  /* n' and m */
+    int32_t n_defined;          /* ids 1 .. M (as everything below) with a finite rhat */
+    int32_t max_rhat_id, min_ess_id;          /* smallest id among equals; 0: there is none */
+    int32_t n_rhat_gt_1p01, n_rhat_gt_1p1;   /* +inf counts */
+    int32_t n_long;             /* transcripts whose lag exceeds L0: finished by the one-wave-per-transcript kernel */
+    double max_rhat, min_ess;   /* over the finite rhat / over the ess that are not NaN; NaN: there is none */
+    double upload_ms, kernel_ms;
+} rsem_gibbs_diag_summary;
+int rsem_gibbs_diagnose(int device, int32_t M, int nchains, const int32_t* nsamples, const int32_t* const* count_vectors,
+                        double* mean, double* sd, double* rhat, double* ess, int32_t* lag /* [M+1] each, any may be NULL */,
+                        rsem_gibbs_diag_summary* summary /* may be NULL */);
+
 /* ---- credibility intervals (rsem-calculate-credibility-intervals) -----------------------------------------
  * Replaces sample_theta_from_c + Buffer (calcCI.cpp:93-164, Buffer.h:13-80) and calcCI / calcCI_batch
  * (calcCI.cpp:216-388): for every Gibbs count vector, nSpC Dirichlet draws theta ~ Dir(c + pseudoC) / mw,

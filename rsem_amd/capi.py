@@ -38,6 +38,12 @@ class GibbsProfile(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("sweep_ms", C.c_double), ("sweeps", C.c_int64), ("chains", C.c_int32), ("team", C.c_int32), ("reduce_ms", C.c_double)]
 
 
+class GibbsDiagSummary(C.Structure):
+    _fields_ = [("n_used", C.c_int32), ("sequences", C.c_int32), ("n_defined", C.c_int32), ("max_rhat_id", C.c_int32),
+                ("min_ess_id", C.c_int32), ("n_rhat_gt_1p01", C.c_int32), ("n_rhat_gt_1p1", C.c_int32), ("n_long", C.c_int32),
+                ("max_rhat", C.c_double), ("min_ess", C.c_double), ("upload_ms", C.c_double), ("kernel_ms", C.c_double)]
+
+
 class EmProfile(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("estep_ms_sum", C.c_double), ("estep_launches", C.c_int32),
                 ("rounds", C.c_int32), ("algorithmic_bytes_per_round", C.c_uint64)]
@@ -95,6 +101,7 @@ def lib():
         L.rsem_comm_allreduce_f64.argtypes = [vp, vp, u64, vp]
         L.rsem_comm_destroy.argtypes = [vp]
         L.rsem_gibbs_chain_seeds.argtypes = [C.c_uint32, ci, _u32p]
+        L.rsem_gibbs_diagnose.argtypes = [ci, i32, ci, vp, vp, vp, vp, vp, vp, vp, vp]
         L.rsem_ci_calculate.argtypes = [ci, i32, i32, i32, _i32p, _f64p, _f64p, dbl, u64, dbl, i32, _i32p, i32, vp,
                                         _f32p, _f32p, _f32p, _f32p, vp, vp, vp]
         L.rsem_ci_sample.argtypes = [ci, i32, i32, i32, _i32p, _f64p, _f64p, dbl, u64, _f32p, _f32p]
@@ -347,6 +354,23 @@ def gibbs_chain_seeds(seed, n):
     out = np.zeros(n, np.uint32)
     _check(lib().rsem_gibbs_chain_seeds(int(seed), n, out))
     return out
+
+
+def gibbs_diagnose(cvs, device=0):
+    """rsem_gibbs_diagnose: split-R-hat and effective sample size of a run's count vectors.  cvs: one (nsamples[k], M+1) int32 array
+    per chain, as GibbsContext.run_chains returns them.  Returns (mean, sd, rhat, ess, lag, summary dict), arrays of M+1."""
+    cvs = [np.ascontiguousarray(a, np.int32) for a in cvs]
+    n = len(cvs)
+    M1 = cvs[0].shape[1] if n else 1
+    assert all(a.ndim == 2 and a.shape[1] == M1 for a in cvs)
+    ns = np.array([a.shape[0] for a in cvs], np.int32)
+    ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in cvs])
+    mean, sd, rhat, ess = (np.zeros(M1) for _ in range(4))
+    lag = np.zeros(M1, np.int32)
+    sm = GibbsDiagSummary()
+    _check(lib().rsem_gibbs_diagnose(device, M1 - 1, n, _ptr(ns), C.cast(ptrs, C.c_void_p), _ptr(mean), _ptr(sd), _ptr(rhat), _ptr(ess),
+                                     _ptr(lag), C.addressof(sm)))
+    return mean, sd, rhat, ess, lag, {k: getattr(sm, k) for k, _ in GibbsDiagSummary._fields_}
 
 
 def ci_intervals(rows, confidence, device=0):

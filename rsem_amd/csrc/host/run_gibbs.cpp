@@ -2,7 +2,7 @@
 //
 //   rsem-run-gibbs refName imdName statName BURNIN NSAMPLES GAP [-p N] [--seed s] [--pseudo-count a]
 //                  [--prior file] [-q]   + ignored-by-the-reference extras:
-//                  [--gibbs-mode auto|exact|parallel] [--gibbs-thin k] [--device d | --devices d0,d1,..]
+//                  [--gibbs-mode auto|exact|parallel] [--gibbs-thin k] [--device d | --devices d0,d1,..] [--diagnostics]
 //
 // -p N keeps its meaning "N independent chains, N count-vector files" (Gibbs.cpp:211-226, calcCI opens one
 // file per thread).  The chains are dealt to the available GPUs; a GPU advances all of its chains together (one wave
@@ -29,13 +29,13 @@ using namespace rsemh;
 int main(int argc, char* argv[]) {
     if (argc < 7) {
         printf("Usage: rsem-run-gibbs reference_name imdName statName BURNIN NSAMPLES GAP [-p #Threads] [--seed seed] "
-               "[--pseudo-count pseudo_count] [--prior file] [-q] [--gibbs-mode auto|exact|parallel] [--gibbs-thin k] [--device d]\n");
+               "[--pseudo-count pseudo_count] [--prior file] [-q] [--gibbs-mode auto|exact|parallel] [--gibbs-thin k] [--device d] [--diagnostics]\n");
         exit(-1);
     }
     const std::string refName = argv[1], imdName = argv[2], statName = argv[3];
     const int BURNIN = atoi(argv[4]), NSAMPLES = atoi(argv[5]), GAP = atoi(argv[6]);
     int nThreads = 1, thin = 0, device = -1;
-    bool hasSeed = false, quiet = false, has_prior = false, dry_run = false;
+    bool hasSeed = false, quiet = false, has_prior = false, dry_run = false, diagnostics = false;
     uint32_t seed = 0;
     double pseudoC = 1.0;
     std::string fprior, mode_s = "auto", devices_s;
@@ -53,6 +53,7 @@ int main(int argc, char* argv[]) {
         if (!strcmp(argv[i], "--gibbs-thin") && i + 1 < argc) thin = atoi(argv[i + 1]);
         if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[i + 1]);
         if (!strcmp(argv[i], "--devices") && i + 1 < argc) devices_s = argv[i + 1];
+        if (!strcmp(argv[i], "--diagnostics")) diagnostics = true;  // split-R-hat and effective sample size of the chains -> statName.gibbs_diag
         if (!strcmp(argv[i], "--dry-run")) dry_run = true;  // load the inputs, print the sampler that would run, exit (no GPU work)
     }
     const bool verbose = !quiet;
@@ -236,6 +237,7 @@ int main(int argc, char* argv[]) {
     std::vector<double> pme_c(M + 1, 0.0), pve_c(M + 1, 0.0), pme_tpm(M + 1, 0.0), pme_fpkm(M + 1, 0.0), pve_c_genes(gi.m, 0.0);
     std::vector<double> pve_c_trans(m_trans, 0.0);
     std::vector<std::string> errors(nworkers);
+    std::vector<std::vector<int32_t>> kept_cv(diagnostics ? nThreads : 0);  // --diagnostics: the chains' count vectors outlive their workers
     std::vector<std::thread> workers;
     for (int w = 0; w < nworkers; w++) {
         workers.emplace_back([&, w]() {
@@ -295,6 +297,7 @@ int main(int argc, char* argv[]) {
                 }
                 fclose(fo);
                 if (verbose) printf("Chain %d is finished!\n", k);
+                if (diagnostics) kept_cv[k].swap(cv[j]);
             }
             rsem_gibbs_destroy(g);
         });
@@ -313,5 +316,34 @@ int main(int argc, char* argv[]) {
     if (verbose) printf("Gibbs finished!\n");
     write_results_gibbs(M, gi, imdName, pme_c, pme_fpkm, pme_tpm, pve_c, pve_c_genes, alleleS, &gt, &ta, &pve_c_trans);
     if (verbose) printf("Gibbs based expression values are written!\n");
+    if (diagnostics) {
+        // convergence of the chains that just ran (include/rsem_hip.h: rsem_gibbs_diagnose), on the run's first device
+        std::vector<int32_t> ns(nThreads);
+        std::vector<const int32_t*> ptrs(nThreads);
+        for (int k = 0; k < nThreads; k++) { ns[k] = quotient + (k < left ? 1 : 0); ptrs[k] = kept_cv[k].data(); }
+        std::vector<double> d_mean(M + 1), d_sd(M + 1), d_rhat(M + 1), d_ess(M + 1);
+        std::vector<int32_t> d_lag(M + 1);
+        rsem_gibbs_diag_summary sm;
+        const int rc = rsem_gibbs_diagnose(devs[0], M, nThreads, ns.data(), ptrs.data(), d_mean.data(), d_sd.data(), d_rhat.data(), d_ess.data(),
+                                           d_lag.data(), &sm);
+        if (rc != RSEM_OK) die("rsem-run-gibbs: --diagnostics: %s: %s", rsem_hip_strerror(rc), rsem_hip_last_error());
+        const Transcripts T = load_transcripts(refName + ".ti");  // the ids the result writers print (results.hpp)
+        if (T.M != M) die("M in %s.ti is not consistent with %s.seq!", refName.c_str(), refName.c_str());
+        FILE* fd = fopen((statName + ".gibbs_diag").c_str(), "w");
+        if (!fd) die("Cannot write %s.gibbs_diag!", statName.c_str());
+        auto num = [](double v) { char b[32]; if (std::isnan(v)) snprintf(b, sizeof b, "NA"); else snprintf(b, sizeof b, "%.6g", v); return std::string(b); };
+        fprintf(fd, "# sampler %s\n# n_used %d\n# sequences %d\n# n_defined %d\n# max_rhat %s\n# max_rhat_id %d\n# min_ess %s\n# min_ess_id %d\n"
+                    "# n_rhat_gt_1p01 %d\n# n_rhat_gt_1p1 %d\n# n_long %d\n# upload_ms %s\n# kernel_ms %s\n",
+                mode == RSEM_GIBBS_EXACT ? "exact" : "parallel", sm.n_used, sm.sequences, sm.n_defined, num(sm.max_rhat).c_str(), sm.max_rhat_id,
+                num(sm.min_ess).c_str(), sm.min_ess_id, sm.n_rhat_gt_1p01, sm.n_rhat_gt_1p1, sm.n_long, num(sm.upload_ms).c_str(), num(sm.kernel_ms).c_str());
+        fprintf(fd, "transcript_id\tmean_count\tsd_count\trhat\tess\tlag\n");
+        for (int i = 1; i <= M; i++)
+            fprintf(fd, "%s\t%s\t%s\t%s\t%s\t%d\n", T.t[i].transcript_id.c_str(), num(d_mean[i]).c_str(), num(d_sd[i]).c_str(), num(d_rhat[i]).c_str(),
+                    num(d_ess[i]).c_str(), d_lag[i]);
+        fclose(fd);
+        if (verbose)
+            printf("Gibbs diagnostics: max_rhat %s, min_ess %s, %d transcript(s) with rhat > 1.01, %d with rhat > 1.1\n", num(sm.max_rhat).c_str(),
+                   num(sm.min_ess).c_str(), sm.n_rhat_gt_1p01, sm.n_rhat_gt_1p1);
+    }
     return 0;
 }
