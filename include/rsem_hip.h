@@ -141,9 +141,11 @@ int rsem_em_get_info(const rsem_em_ctx* ctx, const char* key, int64_t* value);
 int rsem_em_debug_trace(rsem_em_ctx* ctx, const double* theta, unsigned long long* out, uint32_t* n_units_io);
 int rsem_em_destroy(rsem_em_ctx* ctx);
 
-/* One E step + M step.  theta[M+1] in; counts[M+1] out = fractional counts incl. +N0 in bin 0
- * (EM.cpp:385-392), theta_new = counts / sum (EM.cpp:394-398), sum, and the convergence
- * statistics bChange / totNum (EM.cpp:406-413).  Any output pointer may be NULL. */
+/* One E step + M step: round 1 of 1 of rsem_em_run's kernel sequence, over this context's reads alone (no all-reduce).
+ * theta[M+1] in; counts[M+1] out = fractional counts incl. +N0 in bin 0 (EM.cpp:385-392), theta_new = counts / (N0 + the
+ * number of reads with a non-zero normaliser) -- the exact value of the sum the reference divides by (EM.cpp:394-398) --,
+ * sum = the floating-point sum of the counts (the SUM of the reference's ROUND line), and the convergence statistics
+ * bChange / totNum (EM.cpp:406-413).  Any output pointer may be NULL. */
 int rsem_em_step(rsem_em_ctx* ctx, const double* theta, double N0, double* counts,
                  double* theta_new, double* sum, double* bChange, int32_t* totNum);
 

@@ -77,6 +77,7 @@ def lib():
         L.rsem_em_get_values.argtypes = [vp, _f64p, _f64p]
         L.rsem_em_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
         L.rsem_em_get_info.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64)]
+        L.rsem_em_debug_trace.argtypes = [vp, _f64p, vp, C.POINTER(C.c_uint32)]
         L.rsem_em_destroy.argtypes = [vp]
         L.rsem_em_set_comm.argtypes = [vp, vp]
         L.rsem_em_set_progress.argtypes = [vp, vp, vp]
@@ -207,6 +208,13 @@ class EmContext:
         if profile:
             out["profile"] = prof
         return out
+
+    def debug_trace(self, theta):
+        """Per-workgroup (start, end) timestamps of one traced E-step launch, a row per unit in dispatch order."""
+        t = np.zeros((max(self.info("units"), 1), 2), np.uint64)
+        n = C.c_uint32(len(t))
+        _check(lib().rsem_em_debug_trace(self._h, np.ascontiguousarray(theta, np.float64), _ptr(t), C.byref(n)))
+        return t[:n.value]
 
     def expected_weights(self, theta, N0, want_weights=True):
         theta = np.ascontiguousarray(theta, np.float64)

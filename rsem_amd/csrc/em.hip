@@ -21,10 +21,13 @@
 //   * optional Q32 value planes (rsem_em_set_option "value_bits" 32): 4 B per alignment instead of 8 for
 //     the reads that qualify (sell_layout.hpp), the rest stay F64 in shapes of their own;
 //   * the noise bin (touched by every read) never sees a per-read atomic: per-lane register, block
-//     reduction, one partial per workgroup;
-//   * M step + convergence statistics run on the device; a `done` word set by the last
-//     workgroup of the M step freezes theta at exactly the reference's stopping round while the
-//     host only polls it every few rounds (no per-round host sync);
+//     reduction, one atomic per workgroup into one of kTotSlots slots beside the counts; a second set
+//     of slots counts the reads with a non-zero normaliser, so that sum(counts) is known exactly
+//     (N0 + that count) without a reduction: ONE totals protocol for every entry point;
+//   * M step + convergence statistics run on the device (k_mstep_fast, or the closers inside the
+//     lane kernel); no kernel waits on another workgroup; a `done` word set by the last closer to
+//     arrive freezes theta at exactly the reference's stopping round while the host only polls it
+//     every few rounds (no per-round host sync);
 //   * the units of the layout stand in up to three groups (compact / a few ids outside their window / split rows), and the three EM
 //     loops of rsem_em_run (kernel sequence, statistics on a second stream, one launch per round) deal them to launches each in its
 //     own way: unit_groups.hpp is where that dealing is written down; launch_lane below is the one launch site of the lane kernel.
@@ -60,10 +63,9 @@ constexpr int kTotSlots = 64;  // addresses per device-wide total (E-step workgr
 // Ctrl, HostMirror and the closer of a round (also run on the CPU by tests/round_close_emu.cpp)
 #include "round_close.hpp"
 
-// per-workgroup noise partial (for the callers that reduce the partials themselves) and, when `tot` is given, two
-// device-wide totals: tot[0] += v (noise fraction), tot[1] += u (reads with a non-zero normaliser: an integer
-// count, so its total is exact in any order)
-__device__ inline void block_add_totals(double v, double u, double* out_v, double* tot) {
+// the workgroup's share of the two device-wide totals: tot[0] += v (noise fraction), tot[1] += u (reads with a non-zero
+// normaliser: an integer count, so its total is exact in any order)
+__device__ inline void block_add_totals(double v, double u, double* tot) {
     __shared__ double red3[2 * (kBlock / 64)];
     v = wave_sum(v);
     u = wave_sum(u);
@@ -72,12 +74,9 @@ __device__ inline void block_add_totals(double v, double u, double* out_v, doubl
     if (threadIdx.x == 0) {
         double t = 0.0, tu = 0.0;
         for (int i = 0; i < kBlock / 64; i++) { t += red3[i]; tu += red3[kBlock / 64 + i]; }
-        out_v[blockIdx.x] = t;
-        if (tot) {  // kTotSlots addresses per total: a single hot address serialises the whole launch behind it
-            const int slot = blockIdx.x & (kTotSlots - 1);
-            if (t != 0.0) unsafeAtomicAdd(&tot[slot], t);
-            if (tu != 0.0) unsafeAtomicAdd(&tot[kTotSlots + slot], tu);
-        }
+        const int slot = blockIdx.x & (kTotSlots - 1);  // kTotSlots addresses per total: a single hot address serialises the whole launch behind it
+        if (t != 0.0) unsafeAtomicAdd(&tot[slot], t);
+        if (tu != 0.0) unsafeAtomicAdd(&tot[kTotSlots + slot], tu);
     }
 }
 
@@ -89,8 +88,7 @@ __device__ inline void block_add_totals(double v, double u, double* out_v, doubl
 // kernel's.
 __global__ __launch_bounds__(kBlock) void k_estep_long(uint64_t n_rows, const uint32_t* __restrict__ row_list, const uint64_t* __restrict__ row_ptr,
                                                         const int32_t* __restrict__ sid, const double* __restrict__ cp, const double* __restrict__ ncp,
-                                                        const double* __restrict__ theta, double* counts, double* noise_partial, const Ctrl* ctrl,
-                                                        double* totals) {
+                                                        const double* __restrict__ theta, double* counts, const Ctrl* ctrl, double* totals) {
     if (ctrl && ctrl->done) return;
     const int lane = threadIdx.x & 63;
     const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
@@ -119,7 +117,7 @@ __global__ __launch_bounds__(kBlock) void k_estep_long(uint64_t n_rows, const ui
             }
         }
     }
-    block_add_totals(noise, neff, noise_partial, totals);
+    block_add_totals(noise, neff, totals);
 }
 
 // Posterior weight of every alignment in file order (calcExpectedWeights, EM.cpp:237-243): w[j] = f_j / sum_i and
@@ -338,7 +336,7 @@ __device__ inline void solo_close_round(const SoloArgs& A, int M, double N0, con
         acc.add(c, c / sum_c, (praw + (i == 0 ? extra_p : 0.0)) / sum_p);
     });
     close_reduce(acc, scratch);
-    if (threadIdx.x == 0 && close_arrive(A.ctrl, A.mirror, me, n_close, acc, A.stat_round, A.min_round, A.max_round, nullptr))
+    if (threadIdx.x == 0 && close_arrive(A.ctrl, A.mirror, me, n_close, acc, A.stat_round, A.min_round, A.max_round))
         for (int k = 0; k < 2 * kTotSlots; k++) A.prev[n + k] = 0.0;  // the last closer: every other one has read them
 }
 
@@ -368,7 +366,7 @@ __global__ __launch_bounds__(kBlock) void k_estep_lane(
     const Shape* __restrict__ shapes, const Unit* __restrict__ units, uint32_t T, int M,
     const double* __restrict__ theta, const double* __restrict__ tsrc, double N0, const unsigned char* __restrict__ sval,
     const int16_t* __restrict__ sexp, const int32_t* __restrict__ ssid, const double* __restrict__ sncp,
-    const unsigned long long* __restrict__ masks, double* counts, double* noise_partial, double* totals, const Ctrl* ctrl,
+    const unsigned long long* __restrict__ masks, double* counts, double* totals, const Ctrl* ctrl,
     unsigned long long* trace, SoloArgs solo = SoloArgs(), XArgs xa = XArgs()) {
     if (ctrl->done) return;
     if (trace && threadIdx.x == 0) trace[2 * blockIdx.x] = wall_clock64();  // rsem_em_debug_trace only
@@ -480,101 +478,14 @@ __global__ __launch_bounds__(kBlock) void k_estep_lane(
         const double v = cnt_win[i];
         if (v != 0.0) unsafeAtomicAdd(&counts[U.base + i], v);
     }
-    block_add_totals(noise, neff, noise_partial, totals);
+    block_add_totals(noise, neff, totals);
     if (trace && threadIdx.x == 0) trace[2 * blockIdx.x + 1] = wall_clock64();
 }
 
 // ---- M step ----------------------------------------------------------------------------------
 
-__device__ inline double block_sum_det(double v, double* red) {  // deterministic: fixed tree; red: kBlock / 64 doubles of LDS
-    __syncthreads();
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int i = 0; i < kBlock / 64; i++) t += red[i];
-    return t;
-}
-
-// counts[0] += sum(noise partials) + N0 (EM.cpp:392); one workgroup
-__global__ __launch_bounds__(kBlock) void k_add_noise(double N0, double* counts, const double* __restrict__ noise_a, int n_a,
-                                                       const double* __restrict__ noise_b, int n_b) {
-    __shared__ double red[kBlock / 64];
-    double v = 0.0;
-    for (int i = threadIdx.x; i < n_a; i += blockDim.x) v += noise_a[i];
-    for (int i = threadIdx.x; i < n_b; i += blockDim.x) v += noise_b[i];
-    const double t = block_sum_det(v, red);
-    if (threadIdx.x == 0) counts[0] = counts[0] + t + N0;
-}
-
-constexpr int kMstepBlocks = 32;
-static_assert(kCloseMax <= kSumSlots && 2 * kMstepBlocks <= kSumSlots, "every closer has a slot for its share of the sum");
-
-// Fused M step: one launch, <= 32 co-resident workgroups, one grid barrier.
-//   phase 1: counts[0] += noise partials + N0 (EM.cpp:392); per-workgroup partial sums of counts
-//   phase 2: theta = counts / sum (EM.cpp:394-398), convergence statistics (EM.cpp:406-413), counts
-//            zeroed for the next round; the last workgroup evaluates the stop rule (EM.cpp:416).
-__global__ __launch_bounds__(kBlock) void k_mstep_fused(int32_t M, double N0, double* counts,
-                                                         const double* __restrict__ noise_a, int n_a,
-                                                         const double* __restrict__ noise_b, int n_b,
-                                                         double* partials, const double* __restrict__ theta_old,
-                                                         double* theta_new, double* counts_last, Ctrl* ctrl, int round,
-                                                         int min_round, int max_round) {
-    if (ctrl->done) return;
-    const int n = M + 1;
-    const int nb = gridDim.x;
-    const int per = (n + nb - 1) / nb;
-    const int lo = blockIdx.x * per, hi = min(n, lo + per);
-    __shared__ CloseScratch close_lds;  // (phase 1 reduces through its doubles: the barrier stands between the two uses)
-    // phase 1: this workgroup's share of sum(counts) and of the noise partials
-    double v = 0.0;
-    for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) v += counts[i];
-    const double t_counts = block_sum_det(v, close_lds.csum);
-    const int n_noise = n_a + n_b;
-    const int nper = (n_noise + nb - 1) / nb;
-    const int nlo = blockIdx.x * nper, nhi = min(n_noise, nlo + nper);
-    v = 0.0;
-    for (int i = nlo + threadIdx.x; i < nhi; i += blockDim.x) v += (i < n_a) ? noise_a[i] : noise_b[i - n_a];
-    const double t_noise = block_sum_det(v, close_lds.csum);
-    // grid barrier (all workgroups are resident: gridDim <= 32)
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(&partials[blockIdx.x], t_counts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&partials[kMstepBlocks + blockIdx.x], t_noise, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // the only data handed to the other workgroups are these two write-through (agent-scope) stores, and they
-        // are read back with agent-scope loads: draining them before the arrival is all the ordering needed
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_fetch_add(&ctrl->bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        while (__hip_atomic_load(&ctrl->bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)nb) __builtin_amdgcn_s_sleep(1);
-    }
-    __syncthreads();
-    // lanes 0..31 of wave 0 load the count partials, lanes 32..63 the noise partials; fixed summation order
-    __shared__ double s_sum[2];
-    if (threadIdx.x < 64) {
-        const int li = threadIdx.x & 31;
-        double pv = (li < nb) ? __hip_atomic_load(&partials[(threadIdx.x < 32 ? 0 : kMstepBlocks) + li], __ATOMIC_RELAXED,
-                                                  __HIP_MEMORY_SCOPE_AGENT)
-                              : 0.0;
-        for (int d = 1; d < 32; d <<= 1) pv += __shfl_xor(pv, d);
-        if (threadIdx.x == 0) s_sum[0] = pv;
-        if (threadIdx.x == 32) s_sum[1] = pv;
-    }
-    __syncthreads();
-    const double extra0 = s_sum[1] + N0;      // counts[0] += noise + N0 (EM.cpp:392)
-    const double sum = s_sum[0] + extra0;
-    CloseAcc acc;
-    for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        double c = counts[i] + (i == 0 ? extra0 : 0.0);
-        double th = c / sum;
-        theta_new[i] = th;
-        counts_last[i] = c;
-        counts[i] = 0.0;
-        acc.add(c, th, theta_old[i]);
-    }
-    close_reduce(acc, &close_lds);
-    // (the ROUND line's sum is the barrier's, the one theta was divided by)
-    if (threadIdx.x == 0 && close_arrive(ctrl, nullptr, (int)blockIdx.x, nb, acc, round, min_round, max_round, &sum))
-        RSEM_AGENT_STORE(&ctrl->bar, 0u);  // the last workgroup: everybody has left the barrier
-}
+constexpr int kMstepBlocks = 64;  // workgroups of k_mstep_fast at the most (mstep_fast_grid)
+static_assert(kCloseMax <= kSumSlots && kMstepBlocks <= kSumSlots, "every closer has a slot for its share of the sum");
 
 // M step without a grid-wide reduction.  Every read whose normaliser is >= EPSILON contributes fractions that sum to
 // one, so sum(counts) (EM.cpp:395) = N0 + (number of such reads), which the E-step workgroups count on the side
@@ -624,7 +535,7 @@ __global__ __launch_bounds__(kBlock) void k_mstep_fast(int32_t M, double N0, dou
     });
     close_reduce(acc, &close_lds);
     // (the slots' floating-point sum of the counts is for the ROUND line only: theta divides by the exact `sum` above)
-    if (threadIdx.x == 0 && close_arrive(ctrl, mirror, (int)blockIdx.x, nb, acc, round, min_round, max_round, nullptr)) s_last = 1;
+    if (threadIdx.x == 0 && close_arrive(ctrl, mirror, (int)blockIdx.x, nb, acc, round, min_round, max_round)) s_last = 1;
     __syncthreads();
     // the last workgroup to arrive clears the totals for the next round: every workgroup has read them by now
     if (!kFused && s_last && threadIdx.x < 2 * kTotSlots) __hip_atomic_store(&totals[threadIdx.x], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -683,17 +594,13 @@ struct rsem_em_ctx {
     hipStream_t stream_x = nullptr;
     hipEvent_t ev_x_fork = nullptr, ev_x_join = nullptr;
     int x_overlap = 0;            // (measured: +4 % on configs[2] with 10 % cross-gene reads split, -4 % at configs[1]'s size without genes)
-    int noise_n = 0;  // workgroups of the last main E-step launch (= valid entries of d_noise_a)
     // EM state
     double* d_theta[2] = {nullptr, nullptr};
     double* d_red3 = nullptr;     // three buffers of [counts (M+1) | totals (2 * kTotSlots)] (the fused loop rotates them)
     double* d_red = nullptr;      // = d_red3: [counts | totals] in one buffer, so that one all-reduce covers both
     double* d_counts = nullptr;   // = d_red
     double* d_counts_last = nullptr;
-    double* d_noise_a = nullptr;  // per-workgroup noise partials of the main E-step launch
-    double* d_noise_b = nullptr;  // ... of the long-row launch
     double* d_totals = nullptr;   // = d_red + M + 1: kTotSlots slots of the noise fraction, then of the reads with a non-zero normaliser
-    double* d_partials = nullptr;
     double* d_w = nullptr;        // expected-weights scratch (nnz), lazily allocated
     double* d_wn = nullptr;
     Ctrl* d_ctrl = nullptr;
@@ -750,7 +657,7 @@ struct LaneIO {
     const double* tsrc = nullptr;    // ... and their totals
     double N0 = 0.0;
     double* counts = nullptr;
-    double* totals = nullptr;        // the two device-wide totals beside the counts, or nullptr: noise partials per workgroup only
+    double* totals = nullptr;        // the two device-wide totals beside the counts
     unsigned long long* trace = nullptr;  // per-workgroup timestamps, two per unit (tune_unit_order, rsem_em_debug_trace)
     SoloArgs solo;                   // SOLO: the round the closers close (handed to the launch that carries them, no other)
     XArgs xa;                        // PLAIN: the split rows' side arrays
@@ -770,7 +677,7 @@ void launch_lane(rsem_em_ctx* c, Loop loop, bool far_queue, uint32_t u0, uint32_
     const bool closes = loop == Loop::SOLO && !far_queue;
     hipLaunchKernelGGL(lane_kernel(loop, far_queue), dim3(u1 - u0), dim3(kBlock), 0, s, c->L.d_shapes, c->d_units + u0, c->L.T, c->M, io.theta, io.tsrc,
                        io.N0, (const unsigned char*)c->d_sval, (const int16_t*)c->d_sexp, c->L.d_ssid, c->d_sncp, c->L.d_masks, io.counts,
-                       c->d_noise_a + u0, io.totals, (const Ctrl*)c->d_ctrl, io.trace ? io.trace + 2 * (size_t)u0 : nullptr,
+                       io.totals, (const Ctrl*)c->d_ctrl, io.trace ? io.trace + 2 * (size_t)u0 : nullptr,
                        closes ? io.solo : SoloArgs(), io.xa);
 }
 
@@ -797,10 +704,9 @@ int join_x(rsem_em_ctx* c, hipStream_t st) {
 
 // One E step from a plain theta array (the PLAIN loop and every entry point that runs a single step): the lane launches of
 // unit_groups.hpp between the split rows' two side passes, then the reads left in the CSR.  totals: where the workgroups add the two
-// device-wide totals (rsem_em_run), or nullptr.
+// device-wide totals.
 int launch_estep(rsem_em_ctx* c, const double* d_theta, double* d_counts, hipStream_t st, double* d_totals, unsigned long long* d_trace = nullptr) {
     const Ctrl* ctrl = c->d_ctrl;
-    c->noise_n = (int)c->n_units;
     const LanePlan plan = plan_lanes(c, Loop::PLAIN);
     hipStream_t sx = plan.x_second ? c->stream_x : st;  // the split rows' chain: rowsum -> their lane launch -> colsum
     LaneIO io;
@@ -831,14 +737,10 @@ int launch_estep(rsem_em_ctx* c, const double* d_theta, double* d_counts, hipStr
     if (c->L.n_long_rows) {
         hipLaunchKernelGGL(k_estep_long, dim3(c->grid_long), dim3(kBlock), 0, st, (uint64_t)c->L.n_long_rows,
                            (const uint32_t*)(c->L.d_order + c->L.n_sell_rows), (const uint64_t*)c->d_row_ptr, (const int32_t*)c->d_sid, (const double*)c->d_cp,
-                           (const double*)c->d_ncp, d_theta, d_counts, c->d_noise_b, ctrl, d_totals);
+                           (const double*)c->d_ncp, d_theta, d_counts, ctrl, d_totals);
         RSEM_HIP_TRY(hipGetLastError());
     }
     return RSEM_OK;
-}
-
-int n_noise_b(const rsem_em_ctx* c) {
-    return c->L.n_long_rows ? c->grid_long : 0;
 }
 
 int launch_weights(rsem_em_ctx* c, const double* d_theta, hipStream_t st) {
@@ -851,7 +753,37 @@ int launch_weights(rsem_em_ctx* c, const double* d_theta, hipStream_t st) {
 
 // workgroups of k_mstep_fast (either instantiation)
 int mstep_fast_grid(const rsem_em_ctx* c) {
-    return std::max(1, std::min(2 * kMstepBlocks, rsem::ceil_div((uint64_t)c->M + 1, kBlock * 2)));
+    return std::max(1, std::min(kMstepBlocks, rsem::ceil_div((uint64_t)c->M + 1, kBlock * 2)));
+}
+
+// One plain round: the E step from th_old into the context's [counts | totals], their sum over the shards where `comm` is given
+// (EM.cpp:385-389: counts and the two totals in one all-reduce), then k_mstep_fast<false>, which writes th_new, counts_last and the
+// round's line and leaves the scratch clear.  timed: two events around the E step, or nullptr.
+int plain_round(rsem_em_ctx* c, const double* th_old, double* th_new, double N0, int round, int min_round, int max_round, HostMirror* mirror,
+                rsem_comm* comm, const hipEvent_t* timed) {
+    hipStream_t st = c->stream;
+    if (timed) RSEM_HIP_TRY(hipEventRecord(timed[0], st));
+    int rc = launch_estep(c, th_old, c->d_counts, st, c->d_totals);
+    if (rc != RSEM_OK) return rc;
+    if (timed) RSEM_HIP_TRY(hipEventRecord(timed[1], st));
+    if (comm && (rc = rsem::comm_allreduce_sum_f64(comm, c->d_red, (size_t)c->M + 1 + 2 * kTotSlots, st)) != RSEM_OK) return rc;
+    hipLaunchKernelGGL(k_mstep_fast<false>, dim3(mstep_fast_grid(c)), dim3(kBlock), 0, st, c->M, N0, c->d_counts, c->d_totals, th_old, th_new,
+                       c->d_counts_last, c->d_ctrl, round, min_round, max_round, mirror, (double*)nullptr);
+    RSEM_HIP_TRY(hipGetLastError());
+    return RSEM_OK;
+}
+
+// What every entry point that runs an E step starts with.
+int estep_ready(const rsem_em_ctx* c) {
+    if (!c->have_values) { rsem::set_last_error("CSR values were never set"); return RSEM_ERR_STATE; }
+    if (!c->layout_ok) { rsem::set_last_error("the device layout could not be rebuilt after the last change of values / options"); return RSEM_ERR_STATE; }
+    RSEM_HIP_TRY(hipSetDevice(c->device));
+    return RSEM_OK;
+}
+
+// The [counts | totals] scratch, clear: how every entry point finds it and leaves it.
+hipError_t clear_scratch(rsem_em_ctx* c) {
+    return hipMemsetAsync(c->d_red, 0, sizeof(double) * ((size_t)c->M + 1 + 2 * kTotSlots), c->stream);
 }
 
 int build_layout(rsem_em_ctx* c);
@@ -929,8 +861,8 @@ void free_layout(rsem_em_ctx* c) {
     sell_free(c->L);
     hipFree(c->d_rank); hipFree(c->d_xextra); hipFree(c->d_xinv);
     c->d_rank = nullptr; c->d_xextra = nullptr; c->d_xinv = nullptr;
-    hipFree(c->d_sval); hipFree(c->d_sncp); hipFree(c->d_sexp); hipFree(c->d_fill_err); hipFree(c->d_units); hipFree(c->d_noise_a);
-    c->d_sval = nullptr; c->d_sncp = nullptr; c->d_sexp = nullptr; c->d_fill_err = nullptr; c->d_units = nullptr; c->d_noise_a = nullptr;
+    hipFree(c->d_sval); hipFree(c->d_sncp); hipFree(c->d_sexp); hipFree(c->d_fill_err); hipFree(c->d_units);
+    c->d_sval = nullptr; c->d_sncp = nullptr; c->d_sexp = nullptr; c->d_fill_err = nullptr; c->d_units = nullptr;
     c->h_units.clear();
     c->n_units = 0;
     c->layout_has_q32 = false;
@@ -992,21 +924,16 @@ int build_layout(rsem_em_ctx* c) {
     if (const char* e = getenv("RSEM_HIP_TUNE")) c->tune_passes_left = atoi(e);  // tuning knob: 0 disables
     c->n_far_units = 0;
     for (const Unit& u : c->h_units) c->n_far_units += u.pad[0] != 0;
-    // per-workgroup noise partials
-    const size_t noise_cap = std::max<size_t>((size_t)c->n_cus * 8, c->n_units);
-    RSEM_HIP_TRY(dmalloc(&c->d_noise_a, noise_cap));
-    RSEM_HIP_TRY(hipMemsetAsync(c->d_noise_a, 0, sizeof(double) * noise_cap, c->stream));
-
     c->grid_long = std::max(1, std::min<int>(c->n_cus * 8, rsem::ceil_div(c->L.n_long_rows, kBlock / 64)));  // (k_estep_long: a wave per read)
     c->long_nnz = 0;
     if (c->L.n_long_rows) {
-        unsigned long long* d_n = (unsigned long long*)c->d_noise_a;  // (cleared again below)
+        unsigned long long* d_n = (unsigned long long*)c->d_totals;  // (a slot that is clear between E steps: cleared again below)
         hipLaunchKernelGGL(k_sum_row_lengths, dim3(c->grid_long), dim3(kBlock), 0, c->stream, c->L.n_long_rows, c->L.d_order + c->L.n_sell_rows,
                            c->d_row_ptr, d_n);
         RSEM_HIP_TRY(hipGetLastError());
         unsigned long long h = 0;
         RSEM_HIP_TRY(hipMemcpyAsync(&h, d_n, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-        RSEM_HIP_TRY(hipMemsetAsync(c->d_noise_a, 0, sizeof(double), c->stream));
+        RSEM_HIP_TRY(hipMemsetAsync(c->d_totals, 0, sizeof(double), c->stream));
         RSEM_HIP_TRY(hipStreamSynchronize(c->stream));
         c->long_nnz = h;
     }
@@ -1079,7 +1006,6 @@ int rsem_em_create(rsem_em_ctx** out, int device, int32_t M, uint64_t N1, uint64
     c->d_counts = c->d_red;
     c->d_totals = c->d_red + (size_t)M + 1;
     TRY_OR_FAIL(dmalloc(&c->d_counts_last, (size_t)M + 1));
-    TRY_OR_FAIL(dmalloc(&c->d_noise_b, (size_t)c->n_cus * 8));
     TRY_OR_FAIL(hipMemsetAsync(c->d_totals, 0, sizeof(double) * 2 * kTotSlots, c->stream));
     TRY_OR_FAIL(hipHostMalloc((void**)&c->mirror, sizeof(HostMirror), hipHostMallocDefault));
     memset(c->mirror, 0, sizeof(HostMirror));
@@ -1094,10 +1020,8 @@ int rsem_em_create(rsem_em_ctx** out, int device, int32_t M, uint64_t N1, uint64
         TRY_OR_FAIL(hipEventCreateWithFlags(&c->ev_e[i], hipEventDisableTiming));
         TRY_OR_FAIL(hipEventCreateWithFlags(&c->ev_s[i], hipEventDisableTiming));
     }
-    TRY_OR_FAIL(dmalloc(&c->d_partials, 2 * kMstepBlocks));
     TRY_OR_FAIL(dmalloc(&c->d_ctrl, 1));
     TRY_OR_FAIL(hipMemsetAsync(c->d_counts, 0, sizeof(double) * ((size_t)M + 1), c->stream));
-    TRY_OR_FAIL(hipMemsetAsync(c->d_noise_b, 0, sizeof(double) * c->n_cus * 8, c->stream));
     TRY_OR_FAIL(hipMemsetAsync(c->d_ctrl, 0, sizeof(Ctrl), c->stream));
     if (const char* e = getenv("RSEM_HIP_T")) c->forced_T = (uint32_t)atoi(e);  // tuning knob: slices per block
     rc = build_layout(c);
@@ -1321,10 +1245,10 @@ int rsem_em_debug_trace(rsem_em_ctx* c, const double* theta, unsigned long long*
     RSEM_HIP_TRY(hipMemsetAsync(c->d_ctrl, 0, sizeof(Ctrl), c->stream));
     int rc = RSEM_OK;
     for (int rep = 0; rep < 3 && rc == RSEM_OK; rep++)  // the last repetition is the one reported (caches warm)
-        rc = launch_estep(c, c->d_theta[0], c->d_counts, c->stream, nullptr, d);
+        rc = launch_estep(c, c->d_theta[0], c->d_counts, c->stream, c->d_totals, d);
     hipError_t e = hipMemcpyAsync(out, d, sizeof(unsigned long long) * 2 * c->n_units, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipMemsetAsync(c->d_counts, 0, sizeof(double) * ((size_t)c->M + 1), c->stream);
+    (void)clear_scratch(c);
     (void)hipStreamSynchronize(c->stream);
     (void)hipFree(d);
     if (e != hipSuccess) { rsem::set_last_error("trace download failed"); return RSEM_ERR_HIP; }
@@ -1344,7 +1268,7 @@ int rsem_em_destroy(rsem_em_ctx* c) {
     if (c->stream_x) (void)hipStreamDestroy(c->stream_x);
     if (c->ev_x_fork) (void)hipEventDestroy(c->ev_x_fork);
     if (c->ev_x_join) (void)hipEventDestroy(c->ev_x_join);
-    hipFree(c->d_counts_last); hipFree(c->d_noise_a); hipFree(c->d_noise_b); hipFree(c->d_partials);
+    hipFree(c->d_counts_last);
     if (c->mirror) (void)hipHostFree(c->mirror);
     for (int i = 0; i < 2; i++) if (c->lag_ev[i]) (void)hipEventDestroy(c->lag_ev[i]);
     hipFree(c->d_w); hipFree(c->d_wn); hipFree(c->d_ctrl); hipFree(c->d_units);
@@ -1355,8 +1279,8 @@ int rsem_em_destroy(rsem_em_ctx* c) {
 
 // Longest-processing-time-first with MEASURED workgroup lifetimes: one traced E-step launch, then the units are
 // re-sorted by how long they actually ran (tuple changes, window misses and the sid spread make equal-sized units
-// differ 5x), so the launch does not end on a few long-lived workgroups.  Scratch use of d_counts: the caller
-// clears it afterwards.
+// differ 5x), so the launch does not end on a few long-lived workgroups.  Scratch use of [counts | totals]: the
+// caller clears them afterwards.
 static int tune_unit_order(rsem_em_ctx* c, const double* d_theta) {
     while (c->tune_passes_left > 0) {
         --c->tune_passes_left;
@@ -1367,7 +1291,7 @@ static int tune_unit_order(rsem_em_ctx* c, const double* d_theta) {
         std::vector<unsigned long long> t(2 * (size_t)n);
         int rc = RSEM_OK;
         for (int rep = 0; rep < 2 && rc == RSEM_OK; rep++)  // second launch: caches and clocks warm
-            rc = launch_estep(c, d_theta, c->d_counts, c->stream, nullptr, d);
+            rc = launch_estep(c, d_theta, c->d_counts, c->stream, c->d_totals, d);
         hipError_t e = hipMemcpyAsync(t.data(), d, sizeof(unsigned long long) * 2 * n, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         (void)hipFree(d);
@@ -1431,9 +1355,7 @@ int rsem_em_run(rsem_em_ctx* c, double* theta, double N0, int round0, int min_ro
                 double* counts, double* bChange, int32_t* totNum, rsem_em_profile* prof) {
     RSEM_REQUIRE(c && theta, "NULL argument");
     RSEM_REQUIRE(max_round > round0, "max_round must exceed round0");
-    if (!c->have_values) { rsem::set_last_error("CSR values were never set"); return RSEM_ERR_STATE; }
-    if (!c->layout_ok) { rsem::set_last_error("the device layout could not be rebuilt after the last change of values / options"); return RSEM_ERR_STATE; }
-    RSEM_HIP_TRY(hipSetDevice(c->device));
+    if (int rc0 = estep_ready(c); rc0 != RSEM_OK) return rc0;
     hipStream_t st = c->stream;
     const size_t nb = sizeof(double) * ((size_t)c->M + 1);
     RSEM_HIP_TRY(hipMemcpyAsync(c->d_theta[round0 & 1], theta, nb, hipMemcpyHostToDevice, st));
@@ -1442,8 +1364,7 @@ int rsem_em_run(rsem_em_ctx* c, double* theta, double N0, int round0, int min_ro
         int trc = tune_unit_order(c, c->d_theta[round0 & 1]);
         if (trc != RSEM_OK) return trc;
     }
-    RSEM_HIP_TRY(hipMemsetAsync(c->d_counts, 0, nb, st));
-    RSEM_HIP_TRY(hipMemsetAsync(c->d_totals, 0, sizeof(double) * 2 * kTotSlots, st));
+    RSEM_HIP_TRY(clear_scratch(c));  // (the tuning launches used it)
     const int timed = prof ? std::min(max_round - round0, kMaxTimedRounds) : 0;
     if (prof) {
         while ((int)c->events.size() < 2 * timed + 2) {
@@ -1557,17 +1478,9 @@ int rsem_em_run(rsem_em_ctx* c, double* theta, double N0, int round0, int min_ro
             RSEM_HIP_TRY(hipEventRecord(c->ev_s[r & 3], st2));
             st_stats = st2;
         } else {
-            if (prof && ti < timed) RSEM_HIP_TRY(hipEventRecord(c->events[2 + 2 * ti], st));
-            rc = launch_estep(c, th_old, c->d_counts, st, c->d_totals);
+            rc = plain_round(c, th_old, th_new, N0, r, min_round, max_round, mir, sharded ? c->comm : nullptr,
+                             prof && ti < timed ? &c->events[2 + 2 * ti] : nullptr);
             if (rc != RSEM_OK) return rc;
-            if (prof && ti < timed) RSEM_HIP_TRY(hipEventRecord(c->events[3 + 2 * ti], st));
-            if (sharded) {  // EM.cpp:385-389 across shards: counts and the two totals in one all-reduce
-                rc = rsem::comm_allreduce_sum_f64(c->comm, c->d_red, R, st);
-                if (rc != RSEM_OK) return rc;
-            }
-            hipLaunchKernelGGL(k_mstep_fast<false>, dim3(mstep_fast_grid(c)), dim3(kBlock), 0, st, c->M, N0, c->d_counts, c->d_totals, th_old, th_new,
-                               c->d_counts_last, c->d_ctrl, r, min_round, max_round, mir, (double*)nullptr);
-            RSEM_HIP_TRY(hipGetLastError());
         }
         const bool checkpoint = ((r - round0) % c->check_every == 0) || r == last_launch;
         if (sharded) {
@@ -1631,21 +1544,15 @@ int rsem_em_run(rsem_em_ctx* c, double* theta, double N0, int round0, int min_ro
 int rsem_em_step(rsem_em_ctx* c, const double* theta, double N0, double* counts, double* theta_new, double* sum,
                  double* bChange, int32_t* totNum) {
     RSEM_REQUIRE(c && theta, "NULL argument");
-    if (!c->have_values) { rsem::set_last_error("CSR values were never set"); return RSEM_ERR_STATE; }
-    if (!c->layout_ok) { rsem::set_last_error("the device layout could not be rebuilt after the last change of values / options"); return RSEM_ERR_STATE; }
-    RSEM_HIP_TRY(hipSetDevice(c->device));
+    if (int rc0 = estep_ready(c); rc0 != RSEM_OK) return rc0;
     hipStream_t st = c->stream;
     const size_t nb = sizeof(double) * ((size_t)c->M + 1);
     RSEM_HIP_TRY(hipMemcpyAsync(c->d_theta[0], theta, nb, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemsetAsync(c->d_ctrl, 0, sizeof(Ctrl), st));
-    RSEM_HIP_TRY(hipMemsetAsync(c->d_counts, 0, nb, st));
-    int rc = launch_estep(c, c->d_theta[0], c->d_counts, st, nullptr);
+    RSEM_HIP_TRY(clear_scratch(c));
+    // round 1 of 1 of the PLAIN loop, this context's reads alone: a caller with several shards adds their counts up itself
+    int rc = plain_round(c, c->d_theta[0], c->d_theta[1], N0, 1, 1, 1, nullptr, nullptr, nullptr);
     if (rc != RSEM_OK) return rc;
-    // (round 1 of 1: the M step reduces the per-workgroup noise partials itself)
-    const int grid = std::max(1, std::min(kMstepBlocks, rsem::ceil_div((uint64_t)c->M + 1, kBlock * 4)));
-    hipLaunchKernelGGL(k_mstep_fused, dim3(grid), dim3(kBlock), 0, st, c->M, N0, c->d_counts, c->d_noise_a, c->noise_n, c->d_noise_b, n_noise_b(c),
-                       c->d_partials, (const double*)c->d_theta[0], c->d_theta[1], c->d_counts_last, c->d_ctrl, 1, 1, 1);
-    RSEM_HIP_TRY(hipGetLastError());
     Ctrl h;
     RSEM_HIP_TRY(hipMemcpyAsync(&h, c->d_ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, st));
     if (counts) RSEM_HIP_TRY(hipMemcpyAsync(counts, c->d_counts_last, nb, hipMemcpyDeviceToHost, st));
@@ -1659,9 +1566,7 @@ int rsem_em_step(rsem_em_ctx* c, const double* theta, double N0, double* counts,
 
 int rsem_em_expected_weights(rsem_em_ctx* c, const double* theta, double N0, double* counts, double* w, double* w_noise) {
     RSEM_REQUIRE(c && theta, "NULL argument");
-    if (!c->have_values) { rsem::set_last_error("CSR values were never set"); return RSEM_ERR_STATE; }
-    if (!c->layout_ok) { rsem::set_last_error("the device layout could not be rebuilt after the last change of values / options"); return RSEM_ERR_STATE; }
-    RSEM_HIP_TRY(hipSetDevice(c->device));
+    if (int rc0 = estep_ready(c); rc0 != RSEM_OK) return rc0;
     hipStream_t st = c->stream;
     const size_t nb = sizeof(double) * ((size_t)c->M + 1);
     if (w || w_noise) { int rc0 = ensure_csr(c); if (rc0 != RSEM_OK) return rc0; }  // (the weights pass walks the caller-order CSR)
@@ -1669,20 +1574,22 @@ int rsem_em_expected_weights(rsem_em_ctx* c, const double* theta, double N0, dou
     if ((w || w_noise) && !c->d_wn) RSEM_HIP_TRY(dmalloc(&c->d_wn, c->N1));
     RSEM_HIP_TRY(hipMemcpyAsync(c->d_theta[0], theta, nb, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemsetAsync(c->d_ctrl, 0, sizeof(Ctrl), st));
-    RSEM_HIP_TRY(hipMemsetAsync(c->d_counts, 0, nb, st));
-    // counts: the main E-step kernel (same launch as every theta-only round); weights: their own file-order pass
-    int rc = launch_estep(c, c->d_theta[0], c->d_counts, st, nullptr);
+    RSEM_HIP_TRY(clear_scratch(c));
+    // counts: the main E-step kernel (same launch as every theta-only round), then + noise + N0 in bin 0 (EM.cpp:392) as the SOLO
+    // loop finishes a round (the theta it writes beside them goes to the spare buffer); weights: their own file-order pass
+    int rc = launch_estep(c, c->d_theta[0], c->d_counts, st, c->d_totals);
     if (rc != RSEM_OK) return rc;
-    hipLaunchKernelGGL(k_add_noise, dim3(1), dim3(kBlock), 0, st, N0, c->d_counts, c->d_noise_a, c->noise_n, c->d_noise_b, n_noise_b(c));
+    hipLaunchKernelGGL(k_solo_finish, dim3(rsem::ceil_div((uint64_t)c->M + 1, kBlock)), dim3(kBlock), 0, st, c->M, N0, (const double*)c->d_red,
+                       c->d_theta[1], c->d_counts_last);
     RSEM_HIP_TRY(hipGetLastError());
     if ((w || w_noise) && c->N1) {
         rc = launch_weights(c, c->d_theta[0], st);
         if (rc != RSEM_OK) return rc;
     }
-    if (counts) RSEM_HIP_TRY(hipMemcpyAsync(counts, c->d_counts, nb, hipMemcpyDeviceToHost, st));
+    if (counts) RSEM_HIP_TRY(hipMemcpyAsync(counts, c->d_counts_last, nb, hipMemcpyDeviceToHost, st));
     if (w && c->nnz) RSEM_HIP_TRY(hipMemcpyAsync(w, c->d_w, sizeof(double) * c->nnz, hipMemcpyDeviceToHost, st));
     if (w_noise && c->N1) RSEM_HIP_TRY(hipMemcpyAsync(w_noise, c->d_wn, sizeof(double) * c->N1, hipMemcpyDeviceToHost, st));
-    RSEM_HIP_TRY(hipMemsetAsync(c->d_counts, 0, nb, st));
+    RSEM_HIP_TRY(clear_scratch(c));
     RSEM_HIP_TRY(hipStreamSynchronize(st));
     return RSEM_OK;
 }

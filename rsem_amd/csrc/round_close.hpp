@@ -1,7 +1,7 @@
 // round_close.hpp -- closing an EM round: the convergence statistics of EM.cpp:400-416, the stop rule and the ROUND line, once.
 //
 // A round is closed by n_closers workgroups, each over a slice of the transcripts: the closers in the prologue of
-// k_estep_lane<true, true> and k_solo_close (SOLO loop), k_mstep_fast (PLAIN and FUSED loops) and k_mstep_fused (rsem_em_step).
+// k_estep_lane<true, true> and k_solo_close (SOLO loop) and k_mstep_fast (PLAIN and FUSED loops, rsem_em_step).
 // Each of them walks its slice (SliceWalk), gathers the statistics per thread (CloseAcc), reduces them over the workgroup
 // (close_reduce) and lets thread 0 arrive (close_arrive); the last one to arrive publishes the round.  What a caller keeps:
 // how it forms a count and theta, which buffer it clears, where theta goes and who clears which totals.
@@ -15,7 +15,6 @@
 struct Ctrl {  // device-resident loop control, one per ctx
     int done;
     int final_round;
-    unsigned int bar;         // grid barrier of the fused M-step kernel
     unsigned long long bbits; // accumulating max |dtheta|/theta as ordered bits
     double last_sum;
     double last_bchange;
@@ -41,8 +40,7 @@ struct HostMirror {
     RoundStat hist[kHistCap];
 };
 
-// One thread's share of a slice.  c and th are the caller's: the closers form them differently (exact integer total
-// against barrier sum).
+// One thread's share of a slice.  c and th are the caller's: the closers form them from different buffers.
 struct CloseAcc {
     int tot = 0;
     double bmax = 0.0, csum = 0.0;
@@ -125,10 +123,10 @@ RSEM_DEVFN unsigned int zero_after(unsigned int x) {
 // of the floating-point sum of the counts, the reference's SUM, EM.cpp:394-398,415, into its slot) and one returning add
 // that carries both its count and its arrival and follows the other two by a data dependency.  The last to arrive
 // publishes the round -- Ctrl::last_*, the stop rule (EM.cpp:416), the host's line and THEN the counters that announce it
-// -- and leaves bbits / tick2 clean for the next round.  sum_override: the sum to report instead of the slots' (a caller
-// that divided by a sum of its own).  Returns whether this closer was the last (the caller clears what is its own).
+// -- and leaves bbits / tick2 clean for the next round.  Returns whether this closer was the last (the caller clears what is
+// its own).
 RSEM_DEVFN bool close_arrive(Ctrl* ctrl, HostMirror* mirror, int me, int n_closers, const CloseAcc& acc, int round, int min_round,
-                             int max_round, const double* sum_override) {
+                             int max_round) {
     unsigned int zero = 0;
     if (acc.bmax > 0.0) zero = zero_after((unsigned int)RSEM_AGENT_FETCH_MAX(&ctrl->bbits, (unsigned long long)RSEM_DOUBLE_AS_LL(acc.bmax)));
     zero += zero_after((unsigned int)RSEM_DOUBLE_AS_LL(RSEM_AGENT_EXCHANGE(&ctrl->fslot[me], acc.csum)));
@@ -137,9 +135,7 @@ RSEM_DEVFN bool close_arrive(Ctrl* ctrl, HostMirror* mirror, int me, int n_close
     const int totNum = (int)(old >> 32) + acc.tot;
     const double bchange = RSEM_LL_AS_DOUBLE((long long)RSEM_AGENT_LOAD(&ctrl->bbits));
     double fsum = 0.0;
-    if (sum_override) fsum = *sum_override;
-    else
-        for (int i = 0; i < n_closers; i++) fsum += RSEM_AGENT_LOAD(&ctrl->fslot[i]);
+    for (int i = 0; i < n_closers; i++) fsum += RSEM_AGENT_LOAD(&ctrl->fslot[i]);
     ctrl->last_sum = fsum;
     ctrl->last_bchange = bchange;
     ctrl->last_totNum = totNum;

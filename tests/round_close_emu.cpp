@@ -8,9 +8,8 @@
 //   round_close_emu edges  N_CLOSERS N_ORDERS   n = 300 with elements ON the two thresholds of EM.cpp:406-411
 //
 // Per n: three consecutive rounds on one Ctrl (rounds 1023, 1024, 1025: the ring of the host's lines wraps) under N_ORDERS orders
-// of arrival -- the first two are "closer n-1 last" and "closer 0 last" -- with min_round = 1024 and max_round = 1025; then, two
-// orders each, the same with a sum handed in (sum_override) and a run whose theta does not move (totNum = 0: round 1023 goes on
-// because it is below min_round, round 1024 stops).  Everything is compared with serial() below: the reference's lines
+// of arrival -- the first two are "closer n-1 last" and "closer 0 last" -- with min_round = 1024 and max_round = 1025; then, under
+// two orders, a run whose theta does not move (totNum = 0: round 1023 goes on because it is below min_round, round 1024 stops).  Everything is compared with serial() below: the reference's lines
 // (EM.cpp:400-416) written out, and the slot-order sum spelled as loops over arrays.
 // Prints "ok" or lines starting with "BAD".  Build (tests/test_round_close_emu_cpu.py): hipcc -DRSEM_EMU tests/round_close_emu.cpp -lpthread
 // A closer is some forty barriers and a case tens of thousands of closers: with the machine's default barrier (a sleep and a
@@ -79,8 +78,6 @@ struct Run {  // one n under one order of arrival
     int n = 0, n_closers = 0, round0 = 1022, min_round = 1024, max_round = 1025;
     RoundData* rounds = nullptr;  // [3]
     std::vector<int> order;
-    bool with_override = false;
-    double override_sum = 0.0;
     int bad = 0;
     Ctrl ctrl;
     HostMirror mirror;
@@ -92,15 +89,14 @@ struct Run {  // one n under one order of arrival
 #define CHECK(cond, what)                                                                                                      \
     do {                                                                                                                       \
         if (!(cond)) {                                                                                                         \
-            printf("BAD n %d closers %d round %d last closer %d%s: %s\n", J->n, J->n_closers, round, J->order.back(),          \
-                   J->with_override ? " (override)" : "", what);                                                               \
+            printf("BAD n %d closers %d round %d last closer %d: %s\n", J->n, J->n_closers, round, J->order.back(), what);      \
             ++J->bad;                                                                                                          \
         }                                                                                                                      \
     } while (0)
 
 static void check_round(Run* J, int round, const RoundData& R) {
     const Ctrl& c = J->ctrl;
-    const double want_sum = J->with_override ? J->override_sum : R.slot_sum;
+    const double want_sum = R.slot_sum;
     CHECK(J->n_last == 1 && J->last_me == J->order.back(), "exactly the closer that arrived last must see itself as the last");
     CHECK(c.last_totNum == R.tot, "totNum");
     CHECK(same_bits(c.last_bchange, R.bmax), "bChange");
@@ -128,8 +124,7 @@ static void thread_body(Run* J, int tid) {
             CloseAcc acc;
             walk.each(R.counts.data(), R.old.data(), [&](int, double c, double old) { acc.add(c, c / R.sum, old); });
             close_reduce(acc, &J->scratch);
-            if (tid == 0 && close_arrive(&J->ctrl, &J->mirror, me, J->n_closers, acc, round, J->min_round, J->max_round,
-                                         J->with_override ? &J->override_sum : nullptr)) {
+            if (tid == 0 && close_arrive(&J->ctrl, &J->mirror, me, J->n_closers, acc, round, J->min_round, J->max_round)) {
                 ++J->n_last;
                 J->last_me = me;
             }
@@ -227,18 +222,16 @@ int main(int argc, char** argv) {
         std::vector<int> id(n_closers);
         for (int i = 0; i < n_closers; i++) id[i] = i;
         double first_sum[3] = {};
-        for (int o = 0; o < n_orders + 4; o++) {
+        for (int o = 0; o < n_orders + 2; o++) {
             J->order = id;
             if (o % 2 == 1) std::reverse(J->order.begin(), J->order.end());  // closer 0 last (o even: closer n-1 last)
             if (o >= 2 && o < n_orders) {                                      // ... and shuffles
                 for (int i = n_closers - 1; i > 0; i--) std::swap(J->order[i], J->order[(int)(urand() * (i + 1))]);
             }
-            J->with_override = o >= n_orders && o < n_orders + 2;
-            J->override_sum = 12345.678901234567;
-            J->rounds = o >= n_orders + 2 ? quiet : moving;
+            J->rounds = o >= n_orders ? quiet : moving;
             bad += run_one(J);
             // the sum is the same bits under every order (check_round compared it with serial()'s; this is the direct statement)
-            if (J->rounds == moving && !J->with_override) {
+            if (J->rounds == moving) {
                 if (o == 0) first_sum[0] = J->ctrl.last_sum;
                 else if (!same_bits(first_sum[0], J->ctrl.last_sum)) { printf("BAD n %d: the sum depends on the order of arrival\n", n); ++bad; }
             }

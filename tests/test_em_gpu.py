@@ -107,6 +107,11 @@ def test_synthetic_with_long_rows(variant):
     assert np.allclose(counts, oc, rtol=1e-9, atol=1e-9)
     assert np.allclose(theta_new, oth, rtol=1e-9, atol=1e-15)
     assert t == ot
+    # the lane kernel and the long-row kernel both add to the totals that the counts' noise bin is formed from
+    c2, w, wn = ctx.expected_weights(wl["theta0"], wl["N0"])
+    _, ow, own = orc.em_estep(wl["M"], wl["row_ptr"], wl["sid"], wl["conprb"], wl["ncp"], wl["theta0"], want_weights=True)
+    assert np.allclose(c2, oc, rtol=1e-9, atol=1e-9)
+    assert np.allclose(w, ow, rtol=1e-12, atol=0) and np.allclose(wn, own, rtol=1e-12, atol=0)
     out = ctx.run(wl["theta0"], wl["N0"], max_round=60)
     oth, orounds, ob, ot = orc.em_run(wl["M"], wl["row_ptr"], wl["sid"], wl["conprb"], wl["ncp"], wl["N0"], wl["theta0"],
                                       max_round=60)

@@ -66,7 +66,6 @@ CASES = {
 # the slice a closer must get for the case to sit on the prefetch limit (8 pairs x 256 threads) or one past it: k_mstep_fast runs
 # min(64, ceil((M + 1) / 512)) workgroups (mstep_fast_grid of em.hip), the SOLO loop min(units, 128) closers
 SLICE = {"fast_2048": 2048, "fast_2049": 2049, "solo_2048": 2048, "solo_2049": 2049}
-STEP_CASES = ("few_units", "fast_2048", "fast_2049", "solo_2048", "solo_2049")  # k_mstep_fused with 1 workgroup and with 32
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -103,11 +102,24 @@ def test_every_round_line_of_every_loop(name, monkeypatch):
         thetas[loop] = out["theta"]
     for loop in ("1", "2"):
         assert np.allclose(thetas[loop], thetas["0"], rtol=1e-10, atol=1e-18), loop
-    if name in STEP_CASES:
-        counts, theta_new, s, b, t = ctx.step(wl["theta0"], N0)
-        oc, oth, os_, ob, ot = want[0]
-        assert np.allclose(counts, oc, rtol=1e-9, atol=1e-12)
-        assert np.allclose(theta_new, oth, rtol=1e-9, atol=1e-15)
-        assert abs(s - os_) < 1e-9 * os_
-        assert t == ot and abs(b - ob) <= 1e-9 * max(ob, 1e-12) + 1e-12
+    # the step: round 1 against the oracle ...
+    counts, theta_new, s, b, t = ctx.step(wl["theta0"], N0)
+    oc, oth, os_, ob, ot = want[0]
+    assert np.allclose(counts, oc, rtol=1e-9, atol=1e-12)
+    assert np.allclose(theta_new, oth, rtol=1e-9, atol=1e-15)
+    assert abs(s - os_) < 1e-9 * os_
+    assert t == ot and abs(b - ob) <= 1e-9 * max(ob, 1e-12) + 1e-12
+    # ... and against a one-round run of the PLAIN loop, which it is (not bit for bit: the atomics' order differs between launches)
+    monkeypatch.setenv("RSEM_EM_FUSED", "0")
+    lines = []
+    ctx.set_progress(lambda r, s, b, t: lines.append((r, s, b, t)))
+    one = ctx.run(wl["theta0"], N0, min_round=1, max_round=1)
+    ctx.set_progress(None)
+    assert one["rounds"] == 1 and [l[0] for l in lines] == [1]
+    print(name, "step SUM %.17g bChange %.17g totNum %d / one PLAIN round %.17g %.17g %d" % ((s, b, t) + lines[0][1:]))
+    assert t == one["totNum"] == lines[0][3]
+    assert abs(s - lines[0][1]) <= 1e-9 * abs(lines[0][1])
+    assert abs(b - one["bChange"]) <= 1e-9 * abs(one["bChange"]) and one["bChange"] == lines[0][2]
+    assert np.allclose(theta_new, one["theta"], rtol=1e-10, atol=0)
+    assert np.allclose(counts, one["counts"], rtol=1e-10, atol=0)
     ctx.close()

@@ -229,11 +229,11 @@ def _oracle_weights(g):
 
 @pytest.mark.parametrize("g", ["G2", "G4"])
 def test_entry_points_in_turn_on_one_context(g, monkeypatch):
-    """run -> step -> expected_weights -> run on ONE context, under each loop: only run() has the E-step workgroups add the two
-    device-wide totals (it hands the lane launches the totals' address; the other entry points hand them none and reduce the
-    per-workgroup noise partials), and all of them share the counts / totals scratch.  Totals left behind by a run, or scratch not
-    left as the next entry point expects it, would show in the step's sum and theta or in the second run.  G2: three lane launches
-    per round; G4: split rows, every loop falls back to the kernel sequence."""
+    """run -> step -> expected_weights -> run on ONE context, under each loop: every entry point has the E-step workgroups add the
+    two device-wide totals (noise fraction, reads with a non-zero normaliser) into the slots beside the counts, and each finds that
+    [counts | totals] scratch clear and leaves it clear -- the M-step kernel or a memset does.  Totals or counts left behind by one
+    entry point would show in the next one's noise bin, sum and theta: the step's here, or the second run's.  G2: three lane
+    launches per round; G4: split rows, every loop falls back to the kernel sequence."""
     d = _input(g)
     oc, oth, orounds, ot = _oracle(g, 64)
     ow, own = _oracle_weights(g)
@@ -280,6 +280,10 @@ def test_tuned_unit_order_keeps_the_groups_and_the_results(monkeypatch):
     before = _info(ctx, "G6 built")
     _assert_grouping("G6", before)
     first = ctx.run(d["theta0"], d["N0"], max_round=MAX_ROUND)
+    # the tuning launches of that run added to the totals like every E step: nothing of them is left for the next entry points
+    _check_step(ctx, d, oracle, "G6 step after the tuned run")
+    c2, _, _ = ctx.expected_weights(d["theta0"], d["N0"], want_weights=False)
+    assert np.allclose(c2, oracle[0], rtol=1e-9, atol=1e-9)
     after = _info(ctx, "G6 tuned")
     _assert_grouping("G6", after)
     assert after == before == i0
@@ -288,6 +292,22 @@ def test_tuned_unit_order_keeps_the_groups_and_the_results(monkeypatch):
         assert out["rounds"] == ref["rounds"] == oracle[2] and out["totNum"] == ref["totNum"]
         assert np.allclose(out["theta"], ref["theta"], rtol=1e-10, atol=1e-18)
         assert np.allclose(out["counts"], ref["counts"], rtol=1e-10, atol=1e-9)
+    ctx.close()
+
+
+def test_step_after_a_traced_launch():
+    """G2: rsem_em_debug_trace runs three E-step launches that add to the counts and the totals; the step that follows must find
+    both clear."""
+    d = _input("G2")
+    oc, *_ = _oracle("G2", 64)
+    ctx = _ctx(d)
+    _assert_grouping("G2", _info(ctx, "G2"))
+    t = ctx.debug_trace(d["theta0"])
+    assert t.shape == (ctx.info("units"), 2) and np.all(t[:, 1] >= t[:, 0]) and np.all(t[:, 0] > 0)
+    counts, theta_new, s, _, _ = ctx.step(d["theta0"], d["N0"])
+    assert np.allclose(counts, oc, rtol=1e-9, atol=1e-9)
+    assert abs(s - (d["N0"] + len(d["row_ptr"]) - 1)) < 1e-6, s
+    assert np.allclose(theta_new, oc / oc.sum(), rtol=1e-9, atol=1e-12)
     ctx.close()
 
 

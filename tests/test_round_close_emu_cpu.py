@@ -4,7 +4,7 @@ one after another in shuffled orders of arrival -- against the reference's lines
 The emulator has ONE workgroup: this checks the protocol's logic, not its concurrency.
 
 Per case and order: three consecutive rounds on one Ctrl; totNum equal, bChange and the sum bit for bit (the sum the same under
-every order, or the override), the stop rule, the host's line in its ring entry, bbits / tick2 left clean."""
+every order), the stop rule, the host's line in its ring entry, bbits / tick2 left clean."""
 import os
 import shutil
 import subprocess
