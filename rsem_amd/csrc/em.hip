@@ -367,7 +367,7 @@ __global__ __launch_bounds__(kBlock) void k_estep_lane(
     const double* __restrict__ theta, const double* __restrict__ tsrc, double N0, const unsigned char* __restrict__ sval,
     const int16_t* __restrict__ sexp, const int32_t* __restrict__ ssid, const double* __restrict__ sncp,
     const unsigned long long* __restrict__ masks, double* counts, double* totals, const Ctrl* ctrl,
-    unsigned long long* trace, SoloArgs solo = SoloArgs(), XArgs xa = XArgs()) {
+    unsigned long long* trace, SoloArgs solo = SoloArgs(), XArgs xa = XArgs(), StartList sl = StartList()) {
     if (ctrl->done) return;
     if (trace && threadIdx.x == 0) trace[2 * blockIdx.x] = wall_clock64();  // rsem_em_debug_trace only
     __shared__ double th_win[kWindow];
@@ -407,7 +407,7 @@ __global__ __launch_bounds__(kBlock) void k_estep_lane(
         const uint32_t s_begin = S.slice_base + U.slice_begin + (uint32_t)w * U.per_wave;
         const uint32_t s_end = min(u_end, s_begin + U.per_wave);
 #define RSEM_ESTEP_BLOCK(KK, QQ, FF, XX) \
-    estep_block<KK, kFC, QQ, (QQ ? kQ32Depth[KK - 1] : kF64Depth[KK - 1]), FF, XX>(S, s_begin, s_end, lane, U.base, U.span, theta, tsrc, N0, th_win, cnt_win, sval, sexp, ssid, sncp, masks, counts, noise, neff, M, xa)
+    estep_block<KK, kFC, QQ, (QQ ? kQ32Depth[KK - 1] : kF64Depth[KK - 1]), FF, XX>(S, s_begin, s_end, lane, U.base, U.span, theta, tsrc, N0, th_win, cnt_win, sval, sexp, ssid, sncp, masks, counts, noise, neff, M, xa, FarQueue(), sl)
         // (uniform over the workgroup)  split rows (F64X) only exist where theta is a plain array: the loops that read theta
         // out of the previous round's counts (kFC) are not taken for a layout with split rows (loop_wanted)
 #define RSEM_ESTEP_BLOCK_FQ(KK, QQ, XX) \
@@ -567,6 +567,8 @@ struct rsem_em_ctx {
     int value_range_bits = 8;         // a read qualifies when its non-zero values span less than 2^this
     int short_last_plane = 1;         // reads whose last value plane is a quarter or more empty take a short class (sell_shape.hpp: Shape::cut)
     int short_min_units = kShortClassMinUnits;  // ... where the class fills this many units (short_classes_worth_it)
+    int sid_start_list = 1;           // the launches without far queue take a new tuple's ids from the start list (sell_layout.hpp); 0: from the id planes
+    SidTraffic sid_traffic;           // what those launches then load of ids (partition_units: it follows the unit table)
     bool layout_has_q32 = false;      // the current layout was built with Q32 shapes (from the then-current values)
     bool layout_ok = false;           // false between free_layout and a build_layout that went through (a failed rebuild)
     // the lane kernel's work list (dealt to its launches by unit_groups.hpp)
@@ -647,7 +649,21 @@ int partition_units(rsem_em_ctx* c) {
     if (c->n_units)
         RSEM_HIP_TRY(hipMemcpyAsync(c->d_units, c->h_units.data(), sizeof(Unit) * c->n_units, hipMemcpyHostToDevice, c->stream));
     RSEM_HIP_TRY(hipStreamSynchronize(c->stream));
+    c->sid_traffic = SidTraffic();
+    if (c->L.d_start_list) {
+        const bool far = c->far_queue != 0 && c->n_units_compact < c->n_units_main;  // (the far-queue launch of the PLAIN loop: unit_groups.hpp)
+        return sell_count_sid_traffic(c->L, c->d_units, c->n_units, far ? c->n_units_compact : 0u, far ? c->n_units_main : 0u, c->stream, c->sid_traffic);
+    }
     return RSEM_OK;
+}
+
+// the start list as the launches are handed it: none for the far-queue launch, none with option "sid_start_list" 0
+bool start_list_on(const rsem_em_ctx* c) { return c->sid_start_list != 0 && c->L.d_start_list != nullptr; }
+// bytes of ids one E step loads (rsem_em_get_info "sid_plane_bytes_loaded")
+uint64_t sid_bytes_loaded(const rsem_em_ctx* c) {
+    if (!start_list_on(c)) return c->L.n_sid_planes_loaded * 256;
+    const SidTraffic& t = c->sid_traffic;
+    return 256 * (t.first_planes + t.marked_planes) + 4 * (t.list_entries + t.list_slices);
 }
 
 // ---- the lane kernel's launches ---------------------------------------------------------------------------------------------------------
@@ -675,10 +691,12 @@ LaneKernel lane_kernel(Loop loop, bool far_queue) {
 void launch_lane(rsem_em_ctx* c, Loop loop, bool far_queue, uint32_t u0, uint32_t u1, hipStream_t s, const LaneIO& io) {
     if (u1 <= u0) return;
     const bool closes = loop == Loop::SOLO && !far_queue;
+    StartList sl;
+    if (!far_queue && start_list_on(c)) { sl.list = c->L.d_start_list; sl.off = c->L.d_start_off; }
     hipLaunchKernelGGL(lane_kernel(loop, far_queue), dim3(u1 - u0), dim3(kBlock), 0, s, c->L.d_shapes, c->d_units + u0, c->L.T, c->M, io.theta, io.tsrc,
                        io.N0, (const unsigned char*)c->d_sval, (const int16_t*)c->d_sexp, c->L.d_ssid, c->d_sncp, c->L.d_masks, io.counts,
                        io.totals, (const Ctrl*)c->d_ctrl, io.trace ? io.trace + 2 * (size_t)u0 : nullptr,
-                       closes ? io.solo : SoloArgs(), io.xa);
+                       closes ? io.solo : SoloArgs(), io.xa, sl);
 }
 
 LanePlan plan_lanes(const rsem_em_ctx* c, Loop loop) {
@@ -886,7 +904,7 @@ int build_layout(rsem_em_ctx* c) {
     if (const char* e = getenv("RSEM_HIP_SPLIT_POLICY")) { if (split) split = !strcmp(e, "all") ? 2 : 1; }  // measurement knob
     int rc = sell_build_refined(c->L, c->stream, c->N1, c->M, c->d_row_ptr, c->d_sid, target_waves, c->forced_T,
                                 q32 ? c->d_cp : nullptr, c->value_range_bits, kWindow, units, &c->d_units, &c->n_stray_reads, split,
-                                short_on ? short_min_units : 0);
+                                short_on ? short_min_units : 0, true);
     if (rc != RSEM_OK) return rc;
     if (c->L.n_x_rows) {
         const size_t nxs = (size_t)c->L.n_x_slots;
@@ -1024,6 +1042,9 @@ int rsem_em_create(rsem_em_ctx** out, int device, int32_t M, uint64_t N1, uint64
     TRY_OR_FAIL(hipMemsetAsync(c->d_counts, 0, sizeof(double) * ((size_t)M + 1), c->stream));
     TRY_OR_FAIL(hipMemsetAsync(c->d_ctrl, 0, sizeof(Ctrl), c->stream));
     if (const char* e = getenv("RSEM_HIP_T")) c->forced_T = (uint32_t)atoi(e);  // tuning knob: slices per block
+    // measurement knob: the option's value at creation, 0 = every marked slice reads its id planes (read here alone: what the caller sets
+    // later with rsem_em_set_option holds through every rebuild of the layout)
+    if (const char* e = getenv("RSEM_HIP_SID_START_LIST")) c->sid_start_list = atoi(e) != 0;
     rc = build_layout(c);
     if (rc != RSEM_OK) return fail(rc);
     rsem::thread_stager().release();
@@ -1159,6 +1180,15 @@ int rsem_em_set_option(rsem_em_ctx* c, const char* key, int64_t value) {
         { int rc0 = ensure_csr(c); if (rc0 != RSEM_OK) return rc0; }
         return rebuild_layout(c);
     }
+    if (!strcmp(key, "sid_start_list")) {
+        // 1 (default): in every slice of a wave but its first, the lanes that start a tuple take its ids from the start list (K * n
+        // entries per slice instead of K planes of 64); 0: from the id planes, as the far-queue launch always does.  The list stays
+        // built either way: nothing is laid out again.  (RSEM_HIP_SID_START_LIST only gives the value a context is created with: what
+        // is set here holds through every later rebuild of the layout.)
+        RSEM_REQUIRE(value == 0 || value == 1, "sid_start_list must be 0 or 1");
+        c->sid_start_list = (int)value;
+        return RSEM_OK;
+    }
     if (!strcmp(key, "check_every")) {
         RSEM_REQUIRE(value >= 1 && value <= kHistCap / 4, "check_every out of range");
         c->check_every = (int)value;
@@ -1203,7 +1233,15 @@ int rsem_em_get_info(const rsem_em_ctx* c, const char* key, int64_t* value) {
     else if (!strcmp(key, "unit_bytes")) *value = (int64_t)sizeof(Unit);                 // one record of the unit table (a part of physical_bytes_per_launch)
     else if (!strcmp(key, "sid_plane_bytes")) *value = (int64_t)(c->L.n_planes * 256);
     else if (!strcmp(key, "slots")) *value = c->L.n_slots;
-    else if (!strcmp(key, "sid_plane_bytes_loaded")) *value = (int64_t)(c->L.n_sid_planes_loaded * 256);  // slices where a tuple starts
+    else if (!strcmp(key, "sid_plane_bytes_loaded")) *value = (int64_t)sid_bytes_loaded(c);  // ids of the slices where a tuple starts: planes or list entries
+    else if (!strcmp(key, "sid_start_list")) *value = c->sid_start_list;
+    else if (!strcmp(key, "start_list_entries")) *value = (int64_t)c->L.n_start_entries;     // 0: no list (an empty layout, or 2^32 entries and more)
+    else if (!strcmp(key, "start_list_bytes")) *value = (int64_t)(c->L.d_start_list ? 4 * (c->L.n_start_entries + kStartListPad) + 4 * (uint64_t)c->L.n_slices : 0);
+    // the terms of sid_plane_bytes_loaded with the list on: 256 * (first + marked) + 4 * (entries + slices)
+    else if (!strcmp(key, "sid_first_slice_planes")) *value = (int64_t)c->sid_traffic.first_planes;         // planes of the waves' first slices
+    else if (!strcmp(key, "start_list_entries_loaded")) *value = (int64_t)c->sid_traffic.list_entries;      // entries of their later marked slices
+    else if (!strcmp(key, "start_list_slices")) *value = (int64_t)c->sid_traffic.list_slices;               // slices whose offset is fetched
+    else if (!strcmp(key, "sid_marked_planes_far_queue")) *value = (int64_t)c->sid_traffic.marked_planes;   // planes of the far-queue units' marked slices
     else if (!strcmp(key, "slices")) *value = c->L.n_slices;
     else if (!strcmp(key, "split_rows")) *value = c->L.n_x_rows;    // reads laid out as an in-window row + far entries
     else if (!strcmp(key, "far_entries")) *value = (int64_t)c->L.n_far;
@@ -1213,10 +1251,10 @@ int rsem_em_get_info(const rsem_em_ctx* c, const char* key, int64_t* value) {
         *value = w;
     } else if (!strcmp(key, "physical_bytes_per_launch")) {
         // What one E-step launch of the LANE kernel moves through HBM by construction of the layout: every value plane,
-        // the sid planes of the slices in which a tuple starts, one noise value (and, Q32, one exponent) per row slot, one
+        // the ids of the slices in which a tuple starts (sid_bytes_loaded: the planes, or with the start list the planes of every
+        // wave's first slice, the list entries of its other marked slices and an offset per slice), one noise value (and, Q32, one exponent) per row slot, one
         // mask per slice, the unit table, theta into and counts out of every unit's window, and the CSR entries of the
-        // reads with more than 256 alignments.  (Cache hits are not counted: the first sid slice of a shape, re-read by the
-        // slices without a new tuple, and theta of neighbouring units.)
+        // reads with more than 256 alignments.  (Cache hits are not counted: theta of neighbouring units.)
         int64_t w = 0;
         for (const Unit& u : c->h_units) w += u.span;
         const uint64_t long_nnz = c->long_nnz + (c->L.n_long_rows * 4ull) / 3;  // 12 B per alignment + 16 B per read
@@ -1224,7 +1262,7 @@ int rsem_em_get_info(const rsem_em_ctx* c, const char* key, int64_t* value) {
         // per row slot of the split shapes its far_ptr (8 B) and extra written, read, inv written, read (4 x 8 B; the gathers of
         // inv by the column-order entries stay within a block of slots: cache hits beyond the first)
         const uint64_t far_bytes = 28 * c->L.n_far + 40 * (uint64_t)c->L.n_x_slots;
-        *value = (int64_t)(c->L.val_bytes + c->L.n_sid_planes_loaded * 256 + (uint64_t)c->L.n_slots * (8 + (c->layout_has_q32 ? 2 : 0)) +
+        *value = (int64_t)(c->L.val_bytes + sid_bytes_loaded(c) + (uint64_t)c->L.n_slots * (8 + (c->layout_has_q32 ? 2 : 0)) +
                            (uint64_t)c->L.n_slices * 8 + (uint64_t)c->n_units * sizeof(Unit) + (uint64_t)w * 16 + 16 * ((uint64_t)c->M + 1)) +
                  (int64_t)(12 * long_nnz + far_bytes);
     }

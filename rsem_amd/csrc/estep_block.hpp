@@ -82,6 +82,14 @@ struct FarQueue {
     int* n = nullptr;       // places taken
 };
 
+// The start list (sell_layout.hpp): the ids of the lanes that start a tuple, K * popcount(mask) entries per marked slice, and where
+// each slice's entries begin.  list == nullptr: every marked slice reads its id planes (a caller without a list -- the emulators of
+// tests/ --, a layout whose list was not built, option "sid_start_list" 0).
+struct StartList {
+    const int32_t* list = nullptr;
+    const uint32_t* off = nullptr;  // [slices of the layout]
+};
+
 // one slice's loads: sids (only where a tuple starts), values (doubles, or Q32 mantissas + the read's exponent), noise
 template <int K, bool kQ>
 struct SliceRegs {
@@ -149,7 +157,8 @@ RSEM_DEVFN void estep_block(const Shape& S, uint32_t s_begin, uint32_t s_end, in
                                    const double* __restrict__ theta, const double* __restrict__ tsrc, double N0, double* th_win, double* cnt_win,
                                    const unsigned char* __restrict__ sval, const int16_t* __restrict__ sexp, const int32_t* __restrict__ ssid,
                                    const double* __restrict__ sncp, const unsigned long long* __restrict__ masks,
-                                   double* counts, double& noise, double& neff, int M, const XArgs& X = XArgs(), const FarQueue& FQ = FarQueue()) {
+                                   double* counts, double& noise, double& neff, int M, const XArgs& X = XArgs(), const FarQueue& FQ = FarQueue(),
+                                   const StartList& SL = StartList()) {
     static_assert(!kFQ || kFar, "the far queue belongs to the loop of the units with ids outside their window");
     static_assert(!kFQ || NBUF >= 3, "the far-queue loop requests theta a slice ahead: three register sets at least (the ring loop)");
     using ValT = typename std::conditional<kQ, uint32_t, double>::type;
@@ -158,13 +167,17 @@ RSEM_DEVFN void estep_block(const Shape& S, uint32_t s_begin, uint32_t s_end, in
     const int g = lane & ((1 << lg) - 1);
     const bool g0 = (g == 0);
     const uint32_t R = 64u >> lg;
-    // 64 slices' masks at a time, one per lane
+    // 64 slices' masks at a time, one per lane -- and, with the start list, the 64 slices' offsets into it beside them
+    const bool kList = !kFQ && SL.list != nullptr;  // (uniform over the launch; the far-queue loop reads the ids of every slice: planes)
     uint32_t m_base = s_begin;
     unsigned long long mv = (s_begin + lane < s_end) ? masks[s_begin + lane] : ~0ull;
+    uint32_t ov = 0;
+    if (kList) ov = (s_begin + lane < s_end) ? SL.off[s_begin + lane] : 0u;
     auto mask_of = [&](uint32_t t) -> unsigned long long {
         if (t - m_base >= 64u) {
             m_base = t;
             mv = (t + lane < s_end) ? masks[t + lane] : ~0ull;
+            if (kList) { ov = (t + lane < s_end) ? SL.off[t + lane] : 0u; RSEM_PIN(ov); }
             RSEM_PIN(mv);  // (the wait for this load stays in this rare branch: at the join it would be a wait for everything, every slice)
         }
         const int src = (int)(t - m_base);
@@ -196,10 +209,29 @@ RSEM_DEVFN void estep_block(const Shape& S, uint32_t s_begin, uint32_t s_end, in
         // is slower: 0.971 against 0.936 ms at configs[2], Q32 0.713 against 0.700, profiles/r03t; tried again in round 6 for the
         // units of split rows alone, where a tuple starts in most slices: no difference either way, profiles/r06b_xrows_probe.log,
         // r06c_xrows_probe.log.)
+        // Every slice of a wave but its first takes the ids from the start list, where the context has one: K * n entries (n = the lanes
+        // that start) instead of K * 64.  A lane that does not start loads an entry that exists (its rank clamped to n - 1) and ignores it,
+        // as it ignored its plane entry: still K loads behind the one scalar branch, no lane predicate.  List or planes is a choice
+        // of base pointer, plane stride and lane index -- scalars but for the index --, not a second branch around the loads: one
+        // instruction stream and the same number of loads in flight either way.  The first slice keeps the planes: its mask is
+        // forced to ~0 (a wave may begin in the middle of a block, where the stored mask -- what the list was built from -- is not).
         if (kFQ || m != 0ull) {  // (the far-queue loop reads the ids of every slice: a tuple starts in nearly all of them, and pregather wants no branch)
             const int32_t* __restrict__ ip = ssid + (S.plane_base * 64 + v0);
+            unsigned stride = 64u, idx = ulane;
+            if (!kFQ) {
+                const bool from_list = kList && t != s_begin;  // (uniform over the wave)
+                if (from_list) {
+                    // (mask_of(t) was the last call: the offsets in ov are those of the 64 slices from m_base)
+                    const uint32_t off = (uint32_t)RSEM_READLANE((int)ov, (int)(t - m_base));
+                    const unsigned n = (unsigned)__builtin_popcountll(m);
+                    const unsigned rank = (unsigned)RSEM_MBCNT((uint32_t)m, (uint32_t)(m >> 32));  // set bits below this lane's
+                    ip = SL.list + off;
+                    stride = n;
+                    idx = rank < n ? rank : n - 1u;
+                }
+            }
 #pragma unroll
-            for (int k = 0; k < K; k++) b.id[k] = ip[k * 64 + ulane];
+            for (int k = 0; k < K; k++) b.id[k] = ip[(unsigned)k * stride + idx];
         }
 #pragma unroll
         for (int k = 0; k < K - 1; k++) b.c[k] = stream_load(&vp[k * 64 + ulane]);

@@ -470,9 +470,10 @@ __global__ void k_slice_masks(const Shape* __restrict__ shapes, int n_shapes, ui
     if (lane == 0) masks[s] = m;
 }
 
-// How many sid planes does a pass over the layout fetch?  A slice's sid planes are loaded from HBM only when some lane
-// starts a new tuple there (mask != 0); the other slices re-read the shape's first sid slice (cache hits).  Planes of the
-// slices with a set bit, summed over the layout: the "physical bytes" of the roofline (bench.py) come from this.
+// How many sid planes does a pass over the layout fetch when every marked slice reads its planes?  A slice's sid planes are
+// loaded only when some lane starts a new tuple there (mask != 0: one scalar branch in the loop, estep_block.hpp issue()),
+// then by all 64 lanes; a slice without a start loads no ids at all.  Planes of the slices with a set bit, summed over the
+// layout.  (What a launch loads when the later slices of a block take their ids from the start list: k_count_sid_traffic.)
 __global__ void k_count_sid_planes(const Shape* __restrict__ shapes, int n_shapes, uint32_t n_slices,
                                    const unsigned long long* __restrict__ masks, unsigned long long* out) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -484,6 +485,49 @@ __global__ void k_count_sid_planes(const Shape* __restrict__ shapes, int n_shape
     }
     for (int d = 32; d >= 1; d >>= 1) k += __shfl_xor(k, d);
     if ((threadIdx.x & 63) == 0 && k) atomicAdd(out, k);
+}
+
+// ---- the start list --------------------------------------------------------------------------------------------------------------------
+// A marked slice (mask m != 0) loads K planes of 64 ids, and only the lanes whose bit is set use theirs: 1.7 of 64 on average
+// where a block is long.  The start list holds just those ids: per marked slice, in global slice order, K * n entries
+// (n = popcount(m)), plane k at [k * n, (k + 1) * n), the lane with set bit number `rank` at k * n + rank.  start_off[s] = the
+// exclusive prefix sum of K * n: where slice s's entries begin.  The E step's lane kernel reads the list in every slice but a
+// wave's first (estep_block.hpp issue()); the id planes stay as they are for everything else that reads them.
+constexpr uint32_t kStartListPad = 64 * 4;  // entries behind the last one: a clamped or repeated load never leaves the allocation
+__host__ __device__ inline uint32_t start_list_count(int K, unsigned long long m) { return (uint32_t)K * (uint32_t)__builtin_popcountll(m); }
+// lane `lane` of slice sl (within shape S, mask m, entries from `off`): its K ids to its place in the list, if its read starts a tuple
+__host__ __device__ inline void start_list_fill_lane(const Shape& S, uint32_t sl, int lane, unsigned long long m, uint32_t off,
+                                                     const int32_t* __restrict__ ssid, int32_t* list) {
+    if (((m >> lane) & 1ull) == 0ull) return;
+    const uint32_t n = (uint32_t)__builtin_popcountll(m), rank = (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+    const uint64_t pl0 = (S.plane_base + (uint64_t)sl * S.K) * 64;
+    for (int k = 0; k < S.K; k++) list[(uint64_t)off + (uint32_t)k * n + rank] = ssid[pl0 + (uint64_t)k * 64 + lane];
+}
+__global__ void k_start_counts(const Shape* __restrict__ shapes, int n_shapes, uint32_t n_slices, const unsigned long long* __restrict__ masks,
+                               uint32_t* cnt, unsigned long long* total) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long k = 0;
+    if (s < n_slices) {
+        int sh = 0;
+        while (sh + 1 < n_shapes && s >= shapes[sh + 1].slice_base) ++sh;
+        k = start_list_count(shapes[sh].K, masks[s]);
+        cnt[s] = (uint32_t)k;
+    }
+    for (int d = 32; d >= 1; d >>= 1) k += __shfl_xor(k, d);
+    if ((threadIdx.x & 63) == 0 && k) atomicAdd(total, k);
+}
+__global__ void k_start_fill(const Shape* __restrict__ shapes, int n_shapes, uint32_t n_slices, const unsigned long long* __restrict__ masks,
+                             const uint32_t* __restrict__ start_off, const int32_t* __restrict__ ssid, int32_t* list) {
+    __shared__ Shape sh_shapes[kMaxShapes];
+    for (int i = threadIdx.x; i < n_shapes; i += blockDim.x) sh_shapes[i] = shapes[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const uint32_t s = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
+    if (s >= n_slices) return;
+    int sh = 0;
+    while (sh + 1 < n_shapes && s >= sh_shapes[sh + 1].slice_base) ++sh;
+    const Shape S = sh_shapes[sh];
+    start_list_fill_lane(S, s - S.slice_base, lane, masks[s], start_off[s], ssid, list);
 }
 
 // anchor sid (row_key_of) of the read in row slot 0 of every slice (non-decreasing along the blocks of a shape, except
@@ -656,12 +700,17 @@ struct SellLayout {
     uint32_t* d_slice_minsid = nullptr;
     uint32_t* d_slice_maxsid = nullptr;
     uint32_t* d_slice_maxanchor = nullptr;
+    // the start list (sell_build_start_list: EM contexts only; nullptr: the kernels read the id planes everywhere)
+    uint32_t* d_start_off = nullptr;   // [n_slices]
+    int32_t* d_start_list = nullptr;   // [n_start_entries + kStartListPad]
+    uint64_t n_start_entries = 0;
 };
 
 inline void sell_free(SellLayout& L) {
     hipFree(L.d_order); hipFree(L.d_shapes); hipFree(L.d_ssid); hipFree(L.d_masks); hipFree(L.d_slice_minsid); hipFree(L.d_slice_maxsid); hipFree(L.d_slice_maxanchor);
     hipFree(L.d_xanchor); hipFree(L.d_xreach); hipFree(L.d_far_ptr); hipFree(L.d_far_sid); hipFree(L.d_far_src); hipFree(L.d_far_cp);
     hipFree(L.d_csc_sid); hipFree(L.d_csc_src); hipFree(L.d_csc_slot); hipFree(L.d_csc_cp);
+    hipFree(L.d_start_off); hipFree(L.d_start_list);
     L = SellLayout();
 }
 
@@ -1063,6 +1112,119 @@ inline int sell_flag_far_units(const SellLayout& L, std::vector<Unit>& units, Un
     return RSEM_OK;
 }
 
+// ---- the start list of a finished layout -------------------------------------------------------------------------------------------------
+// Built where masks and id planes are final (the end of sell_build_refined), for EM contexts only: the Gibbs layouts never ask.
+// A list of 2^32 entries or more (with its padding) is not built: start_off is 32 bits wide, and the kernels then read the
+// planes as they always did (d_start_list == nullptr).  The list is an optimisation, so a device too full for it (its entries, the
+// offsets, the counts and the scan's scratch: 70 MB at configs[2]) is no error either: every allocation here that fails leaves
+// the layout without a list.  Only a failure of the device itself (a launch, a copy, the stream) is handed on.
+inline int sell_build_start_list(SellLayout& L, hipStream_t st) {
+    (void)hipFree(L.d_start_off); (void)hipFree(L.d_start_list);
+    L.d_start_off = nullptr; L.d_start_list = nullptr; L.n_start_entries = 0;
+    if (!L.n_slices) return RSEM_OK;
+    uint32_t* d_cnt = nullptr;
+    unsigned long long* d_total = nullptr;
+    void* d_tmp = nullptr;
+    auto cleanup = [&]() { (void)hipFree(d_cnt); (void)hipFree(d_total); (void)hipFree(d_tmp); };
+    unsigned long long total = 0;
+    auto no_list = [&]() {  // (an allocation failed: hipErrorOutOfMemory is not sticky, cleared here)
+        cleanup();
+        (void)hipFree(L.d_start_off); (void)hipFree(L.d_start_list);
+        L.d_start_off = nullptr; L.d_start_list = nullptr;
+        (void)hipGetLastError();
+        return RSEM_OK;
+    };
+    if (dmalloc(&d_cnt, (size_t)L.n_slices) != hipSuccess || dmalloc(&d_total, 1) != hipSuccess) return no_list();
+    hipError_t e = hipMemsetAsync(d_total, 0, sizeof(unsigned long long), st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_start_counts, dim3(rsem::ceil_div(L.n_slices, kBlock)), dim3(kBlock), 0, st, (const Shape*)L.d_shapes, L.n_shapes, L.n_slices,
+                           (const unsigned long long*)L.d_masks, d_cnt, d_total);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { cleanup(); RSEM_HIP_TRY(e); }
+    if (total + kStartListPad >= (1ull << 32)) { cleanup(); return RSEM_OK; }
+    size_t tb = 0;
+    if (dmalloc(&L.d_start_off, (size_t)L.n_slices) != hipSuccess || dmalloc(&L.d_start_list, (size_t)total + kStartListPad) != hipSuccess) return no_list();
+    e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_cnt, L.d_start_off, (int)L.n_slices, st);
+    if (e == hipSuccess && hipMalloc(&d_tmp, tb ? tb : 1) != hipSuccess) return no_list();
+    // (every entry below `total` is written by k_start_fill; the padding behind them is what clamped loads may read)
+    if (e == hipSuccess) e = hipMemsetAsync(L.d_start_list + total, 0, sizeof(int32_t) * kStartListPad, st);
+    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_cnt, L.d_start_off, (int)L.n_slices, st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_start_fill, dim3(rsem::ceil_div(L.n_slices, kBlock / 64)), dim3(kBlock), 0, st, (const Shape*)L.d_shapes, L.n_shapes, L.n_slices,
+                           (const unsigned long long*)L.d_masks, (const uint32_t*)L.d_start_off, (const int32_t*)L.d_ssid, L.d_start_list);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    cleanup();
+    if (e != hipSuccess) {
+        (void)hipFree(L.d_start_off); (void)hipFree(L.d_start_list);
+        L.d_start_off = nullptr; L.d_start_list = nullptr;
+        RSEM_HIP_TRY(e);
+    }
+    L.n_start_entries = total;
+    return RSEM_OK;
+}
+
+// What the lane kernel's launches load of ids when the start list is on, from the unit table as it is launched (one thread per
+// wave of a unit).  Units [fq0, fq1) run the far-queue loop, which keeps the planes: the planes of their marked slices, the
+// rule of k_count_sid_planes.  Every other wave: the full planes of its first slice, the list entries of its later marked
+// slices, and one 32-bit offset per slice.
+struct SidTraffic {
+    unsigned long long first_planes = 0;   // planes (256 B) of the waves' first slices
+    unsigned long long list_entries = 0;   // entries (4 B) of the later marked slices
+    unsigned long long list_slices = 0;    // slices whose offset is fetched (4 B)
+    unsigned long long marked_planes = 0;  // planes (256 B) of the marked slices of the far-queue units
+};
+// wave w of unit U (the unit's waves cut its slices as k_estep_lane does); far_queue: the unit is launched with the far-queue loop.
+// Host-callable like the construction bodies: tests/estep_start_emu.cpp holds it against a count made slice by slice.
+__host__ __device__ inline SidTraffic sid_traffic_of_wave(const Unit& U, uint32_t w, bool far_queue, const unsigned long long* __restrict__ masks) {
+    SidTraffic t;
+    const uint32_t K = (uint32_t)U.S.K;
+    const uint32_t u_end = U.S.slice_base + U.slice_begin + U.n_slices;
+    const uint32_t s_begin = U.S.slice_base + U.slice_begin + w * U.per_wave;
+    if (s_begin >= u_end) return t;
+    const uint32_t s_end = u_end < s_begin + U.per_wave ? u_end : s_begin + U.per_wave;
+    for (uint32_t s = s_begin + (far_queue ? 0u : 1u); s < s_end; s++) {
+        const unsigned long long m = masks[s];
+        if (far_queue) t.marked_planes += m != 0ull ? K : 0u;
+        else t.list_entries += start_list_count((int)K, m);
+    }
+    if (!far_queue) { t.first_planes = K; t.list_slices = s_end - s_begin; }
+    return t;
+}
+__global__ void k_count_sid_traffic(const Unit* __restrict__ units, uint32_t n_units, uint32_t fq0, uint32_t fq1,
+                                    const unsigned long long* __restrict__ masks, unsigned long long* out /* [4]: the fields of SidTraffic */) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, u = i >> 2, w = i & 3;
+    if (u >= n_units) return;
+    const SidTraffic t = sid_traffic_of_wave(units[u], w, u >= fq0 && u < fq1, masks);
+    if (t.first_planes) atomicAdd(&out[0], t.first_planes);
+    if (t.list_entries) atomicAdd(&out[1], t.list_entries);
+    if (t.list_slices) atomicAdd(&out[2], t.list_slices);
+    if (t.marked_planes) atomicAdd(&out[3], t.marked_planes);
+}
+inline int sell_count_sid_traffic(const SellLayout& L, const Unit* d_units, uint32_t n_units, uint32_t fq0, uint32_t fq1, hipStream_t st, SidTraffic& out) {
+    out = SidTraffic();
+    if (!n_units) return RSEM_OK;
+    unsigned long long* d = nullptr;
+    unsigned long long h[4] = {0, 0, 0, 0};
+    RSEM_HIP_TRY(dmalloc(&d, 4));
+    hipError_t e = hipMemsetAsync(d, 0, sizeof(h), st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_count_sid_traffic, dim3(rsem::ceil_div((uint64_t)n_units * 4, kBlock)), dim3(kBlock), 0, st, d_units, n_units, fq0, fq1,
+                           (const unsigned long long*)L.d_masks, d);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(d);
+    RSEM_HIP_TRY(e);
+    out.first_planes = h[0]; out.list_entries = h[1]; out.list_slices = h[2]; out.marked_planes = h[3];
+    return RSEM_OK;
+}
+
 // ---- split rows: every row's window = its UNIT's window ----------------------------------------------------------------------------------
 // A split row keeps the ids inside [anchor, anchor + kLayoutWindow) -- but the unit it lands in stages [base, base + span) only, as wide
 // as its reads' own genes need, and ONE id beyond that sends the whole unit through the loop with the global gather and atomics (kFar:
@@ -1164,7 +1326,7 @@ __global__ __launch_bounds__(256) void k_mark_stray_reads(const Unit* __restrict
 inline int sell_build_refined(SellLayout& L, hipStream_t st, uint64_t N1, int32_t M, const uint64_t* d_row_ptr, const int32_t* d_sid,
                               uint32_t target_waves, uint32_t forced_T, const double* d_cp_for_q32, int range_bits, int window_cap,
                               std::vector<Unit>& units, Unit** d_units, unsigned long long* n_strays = nullptr, int split = 0,
-                              int short_min_units = 0) {
+                              int short_min_units = 0, bool start_list = false /* EM contexts: sell_build_start_list once ids and masks stand */) {
     unsigned char* d_also = nullptr;
     unsigned long long* d_n = nullptr;
     if (n_strays) *n_strays = 0;
@@ -1206,9 +1368,11 @@ inline int sell_build_refined(SellLayout& L, hipStream_t st, uint64_t N1, int32_
         sell_free(L);       // second pass with the marks
     }
     (void)hipFree(d_also);
-    if (L.n_x_rows && !(getenv("RSEM_HIP_X_REFINE") && atoi(getenv("RSEM_HIP_X_REFINE")) == 0))  // (measurement knob: 0 = the rows keep their own windows)
-        return sell_refine_split_windows(L, st, d_row_ptr, d_sid, units, *d_units);
-    return RSEM_OK;
+    if (L.n_x_rows && !(getenv("RSEM_HIP_X_REFINE") && atoi(getenv("RSEM_HIP_X_REFINE")) == 0)) {  // (measurement knob: 0 = the rows keep their own windows)
+        const int rc = sell_refine_split_windows(L, st, d_row_ptr, d_sid, units, *d_units);  // (rewrites the split rows' ids and the masks)
+        if (rc != RSEM_OK) return rc;
+    }
+    return start_list ? sell_build_start_list(L, st) : RSEM_OK;
 }
 
 }  // namespace

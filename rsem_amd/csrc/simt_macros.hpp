@@ -30,6 +30,8 @@
 /* every global load, store and atomic this wave has issued is done -- and the compiler knows it: no "possibly in flight" behind this */
 #define RSEM_WAIT_VM0() __builtin_amdgcn_s_waitcnt(0x0F70) /* vmcnt(0), expcnt and lgkmcnt untouched (gfx9 encoding: vmcnt = bits 15:14 | 3:0) */
 #define RSEM_READFIRSTLANE(v) __builtin_amdgcn_readfirstlane(v)
+/* how many bits of the 64-bit mask hi:lo are set below this lane's own */
+#define RSEM_MBCNT(lo, hi) __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u))
 /* the value must be in its register HERE: the wait for its load is placed at this point and not at a later join of paths */
 #define RSEM_PIN(x) asm volatile("" : "+v"(x))
 /* nothing moves across this point in the instruction schedule */
@@ -52,4 +54,9 @@
 #define RSEM_HOST_RELEASE_STORE(p, v) __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM)
 /* z = 0, computed from x: whatever uses z waits for x to have come back (an ordering by data dependency instead of a fence) */
 #define RSEM_ZERO_DEP(z, x) asm volatile("v_and_b32 %0, 0, %1" : "=v"(z) : "v"(x))
+#else
+/* the emulator's header came first; what it does not define itself is spelled here in plain C++ */
+#ifndef RSEM_MBCNT
+#define RSEM_MBCNT(lo, hi) __builtin_popcountll((((unsigned long long)(hi) << 32) | (unsigned long long)(lo)) & ((1ull << emu::lane()) - 1ull))
+#endif
 #endif
