@@ -327,7 +327,8 @@ int rsem_gibbs_run(rsem_gibbs_ctx* ctx, int mode, uint32_t seed, int burnin, int
                    double* pme_fpkm, double* pve_c_genes, double* sweep_ms /* may be NULL */);
 /* Allele-specific references (ref.ta, GroupInfo.h): ta[m_trans+1] = first allele of every transcript.  After this
  * call every rsem_gibbs_run also accumulates, per kept sample, the squared per-transcript count sums
- * (pve_c_trans, Gibbs.cpp:339-345); rsem_gibbs_get_pve_c_trans returns the last run's sums [m_trans]. */
+ * (pve_c_trans, Gibbs.cpp:339-345); rsem_gibbs_get_pve_c_trans returns the last run's sums [m_trans].  ta, as grp of
+ * rsem_gibbs_create, must start at 1, end at M+1 and never decrease (RSEM_ERR_INVALID, nothing changed). */
 int rsem_gibbs_set_allele_groups(rsem_gibbs_ctx* ctx, int32_t m_trans, const int32_t* ta);
 int rsem_gibbs_get_pve_c_trans(rsem_gibbs_ctx* ctx, double* pve_c_trans);
 /* Chains sharded over GPUs: every later rsem_gibbs_run_chains ends with ONE reduce of its
@@ -412,6 +413,9 @@ int rsem_ci_sample(int device, int32_t M, int32_t nCV, int32_t nSpC, const int32
  * (calcCI, calcCI.cpp:216-284). */
 int rsem_ci_intervals(int device, int64_t nrows, int32_t nSamples, const float* rows, double confidence, float* lb,
                       float* ub, float* cqv);
+/* The interval stage of the three calls above takes its rows in batches of at most 2^30 keys.  The environment variable
+ * RSEM_CI_BATCH_KEYS (a whole number from nSamples to 2^30; anything else: RSEM_ERR_INVALID), read at every call, replaces
+ * the 2^30 (a test knob: the results do not depend on it). */
 
 #ifdef __cplusplus
 }

@@ -91,6 +91,7 @@ def lib():
         L.rsem_gibbs_run_chains.argtypes = [vp, ci, ci, _u32p, ci, _i32p, ci, ci, vp, _f64p, _f64p, _f64p, _f64p, _f64p, vp, vp]
         L.rsem_gibbs_set_comm.argtypes = [vp, vp]
         L.rsem_gibbs_set_allele_groups.argtypes = [vp, i32, _i32p]
+        L.rsem_gibbs_get_pve_c_trans.argtypes = [vp, _f64p]
         L.rsem_gibbs_debug_order.argtypes = [vp, _u32p, _u8p, C.POINTER(C.c_uint32)]
         L.rsem_gibbs_debug_units.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp]
         L.rsem_gibbs_destroy.argtypes = [vp]
@@ -105,6 +106,8 @@ def lib():
         L.rsem_gibbs_diagnose.argtypes = [ci, i32, ci, vp, vp, vp, vp, vp, vp, vp, vp]
         L.rsem_ci_calculate.argtypes = [ci, i32, i32, i32, _i32p, _f64p, _f64p, dbl, u64, dbl, i32, _i32p, i32, vp,
                                         _f32p, _f32p, _f32p, _f32p, vp, vp, vp]
+        L.rsem_ci_calculate_samples.argtypes = [ci, i32, i32, _f32p, _f32p, dbl, i32, _i32p, i32, vp,
+                                                _f32p, _f32p, _f32p, _f32p, vp, vp, vp]
         L.rsem_ci_sample.argtypes = [ci, i32, i32, i32, _i32p, _f64p, _f64p, dbl, u64, _f32p, _f32p]
         L.rsem_ci_intervals.argtypes = [ci, C.c_int64, i32, _f32p, dbl, _f32p, _f32p, _f32p]
         _lib = L
@@ -282,8 +285,15 @@ class GibbsContext:
 
     def set_allele_groups(self, ta):
         ta = np.ascontiguousarray(ta, np.int32)
+        _check(lib().rsem_gibbs_set_allele_groups(self._h, len(ta) - 1, ta))
         self.m_trans = len(ta) - 1
-        _check(lib().rsem_gibbs_set_allele_groups(self._h, self.m_trans, ta))
+
+    def get_pve_c_trans(self):
+        """rsem_gibbs_get_pve_c_trans: the last run's squared per-transcript (over alleles) count sums; RSEM_ERR_STATE when
+        allele groups were never set or no chain has run since."""
+        out = np.zeros(max(getattr(self, "m_trans", 0), 1))
+        _check(lib().rsem_gibbs_get_pve_c_trans(self._h, out))
+        return out[:getattr(self, "m_trans", 0)]
 
     def run_chains(self, mode, seeds, burnin, nsamples, gap, thin=1, want_vectors=True):
         """rsem_gibbs_run_chains: all chains of this GPU in one call.  Returns (list of count-vector arrays or None,
@@ -402,12 +412,7 @@ def ci_sample(cvecs, nSpC, eel, mw, pseudoC=1.0, seed=0, device=0):
     return tpm, lbar
 
 
-def ci_calculate(cvecs, nSpC, eel, mw, gene_starts, confidence=0.95, pseudoC=1.0, seed=0, trans_starts=None, device=0):
-    """rsem-calculate-credibility-intervals in one call.  Returns a dict of (3, n) float32 arrays [lb, ub, cqv]:
-    tpm, fpkm (n = M), gene_tpm, gene_fpkm (n = m) and, with trans_starts, iso_tpm, iso_fpkm; plus 'profile'."""
-    cvecs = np.ascontiguousarray(cvecs, np.int32)
-    nCV, M1 = cvecs.shape
-    M = M1 - 1
+def _ci_outputs(M, gene_starts, trans_starts):
     gs = np.ascontiguousarray(gene_starts, np.int32)
     m = len(gs) - 1
     out = {k: np.zeros((3, n), np.float32) for k, n in (("tpm", M), ("fpkm", M), ("gene_tpm", m), ("gene_fpkm", m))}
@@ -418,10 +423,36 @@ def ci_calculate(cvecs, nSpC, eel, mw, gene_starts, confidence=0.95, pseudoC=1.0
         mt = len(ts) - 1
         out["iso_tpm"] = np.zeros((3, mt), np.float32)
         out["iso_fpkm"] = np.zeros((3, mt), np.float32)
+    return out, gs, m, ts, mt
+
+
+def ci_calculate(cvecs, nSpC, eel, mw, gene_starts, confidence=0.95, pseudoC=1.0, seed=0, trans_starts=None, device=0):
+    """rsem-calculate-credibility-intervals in one call.  Returns a dict of (3, n) float32 arrays [lb, ub, cqv]:
+    tpm, fpkm (n = M), gene_tpm, gene_fpkm (n = m) and, with trans_starts, iso_tpm, iso_fpkm; plus 'profile'."""
+    cvecs = np.ascontiguousarray(cvecs, np.int32)
+    nCV, M1 = cvecs.shape
+    M = M1 - 1
+    out, gs, m, ts, mt = _ci_outputs(M, gene_starts, trans_starts)
     prof = CiProfile()
     _check(lib().rsem_ci_calculate(device, M, nCV, nSpC, cvecs, np.ascontiguousarray(eel, np.float64),
                                    np.ascontiguousarray(mw, np.float64), float(pseudoC), int(seed), float(confidence), m, gs, mt,
                                    _ptr(ts), out["tpm"], out["fpkm"], out["gene_tpm"], out["gene_fpkm"], _ptr(out.get("iso_tpm")),
                                    _ptr(out.get("iso_fpkm")), C.addressof(prof)))
+    out["profile"] = prof
+    return out
+
+
+def ci_calculate_samples(tpm_samples, l_bars, gene_starts, confidence=0.95, trans_starts=None, device=0):
+    """Phase II of calcCI.cpp alone (--ci-stream reference): the intervals of the caller's (M, nSamples) float32 TPM samples and
+    their l_bars.  Returns what ci_calculate returns."""
+    tpm_samples = np.ascontiguousarray(tpm_samples, np.float32)
+    M, nS = tpm_samples.shape
+    l_bars = np.ascontiguousarray(l_bars, np.float32)
+    assert l_bars.shape == (nS,)
+    out, gs, m, ts, mt = _ci_outputs(M, gene_starts, trans_starts)
+    prof = CiProfile()
+    _check(lib().rsem_ci_calculate_samples(device, M, nS, tpm_samples, l_bars, float(confidence), m, gs, mt, _ptr(ts), out["tpm"],
+                                           out["fpkm"], out["gene_tpm"], out["gene_fpkm"], _ptr(out.get("iso_tpm")),
+                                           _ptr(out.get("iso_fpkm")), C.addressof(prof)))
     out["profile"] = prof
     return out

@@ -21,6 +21,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <vector>
 
 #include "common.hpp"
@@ -255,9 +256,20 @@ struct RowSorter {
     }
 };
 
-int64_t batch_rows(int32_t nS, int64_t total) {
-    const int64_t cap = std::max<int64_t>(1, ((int64_t)1 << 30) / nS);  // int offsets in the segmented sort; 4 GB of keys
-    return std::max<int64_t>(1, std::min(total, cap));
+// R = rows per batch of the segmented sort: int offsets, 4 GB of keys.  RSEM_CI_BATCH_KEYS (test knob, read at every call): the
+// most keys a batch may hold instead of 2^30, a whole number from nS to 2^30 -- anything else is an error, not silently the default.
+int batch_rows(int32_t nS, int64_t total, int64_t& R) {
+    int64_t keys = (int64_t)1 << 30;
+    if (const char* e = getenv("RSEM_CI_BATCH_KEYS")) {
+        char* end = nullptr;
+        const unsigned long long v = (e[0] >= '0' && e[0] <= '9') ? strtoull(e, &end, 10) : 0;
+        RSEM_REQUIRE(end && end != e && *end == '\0' && end - e <= 10 && v >= (unsigned long long)nS && v <= (1ull << 30),
+                     "RSEM_CI_BATCH_KEYS must be a whole number from nSamples to 2^30 (1073741824)");
+        keys = (int64_t)v;
+    }
+    const int64_t cap = std::max<int64_t>(1, keys / nS);
+    R = std::max<int64_t>(1, std::min(total, cap));
+    return RSEM_OK;
 }
 
 struct Sampler {  // Y (M x nS, unnormalised), scale and l_bar per sample, on the device
@@ -330,13 +342,14 @@ extern "C" int rsem_ci_intervals(int device, int64_t nrows, int32_t nSamples, co
                                  float* ub, float* cqv) {
     RSEM_REQUIRE(nrows >= 0 && nSamples > 0 && rows && lb && ub && cqv, "bad arguments");
     RSEM_REQUIRE(confidence > 0.0 && confidence <= 1.0, "confidence must be in (0, 1]");
+    int64_t R = 0;
+    int rc = batch_rows(nSamples, std::max<int64_t>(nrows, 1), R);
+    if (rc != RSEM_OK) return rc;
     RSEM_HIP_TRY(hipSetDevice(device));
     StreamGuard sg;
     RSEM_HIP_TRY(sg.create());
     hipStream_t st = sg.s;
-    int rc = RSEM_OK;
     {
-        const int64_t R = batch_rows(nSamples, std::max<int64_t>(nrows, 1));
         RowSorter sorter;
         DevMem mem;
         float* d_keys = nullptr;
@@ -390,8 +403,10 @@ int ci_after_sampling(Sampler& S, int32_t M, int32_t nS, double confidence, int3
     DevMem mem;
     float* d_keys = nullptr;
     int32_t *d_gb = nullptr, *d_ge = nullptr;
-    const int64_t R = batch_rows(nS, M);
-    int rc = sorter.init(nS, R, st);
+    int64_t R = 0;
+    int rc = batch_rows(nS, M, R);
+    if (rc != RSEM_OK) return rc;
+    rc = sorter.init(nS, R, st);
     if (rc == RSEM_OK && (mem.alloc(&d_keys, (size_t)R * nS) != hipSuccess || mem.alloc(&d_gb, (size_t)R) != hipSuccess ||
                           mem.alloc(&d_ge, (size_t)R) != hipSuccess)) {
         rsem::set_last_error("out of device memory"); rc = RSEM_ERR_NOMEM;

@@ -522,6 +522,18 @@ int ensure_parallel_layout(rsem_gibbs_ctx* c) {
     return RSEM_OK;
 }
 
+// grp / ta: the starts of consecutive groups over the ids 1..M.  k_gibbs_group_stats walks counts[] from one start to the next, so
+// an array that does not run from 1 to M + 1 without ever decreasing would make it read outside the count vector.
+int check_group_starts(int32_t M, int32_t n, const int32_t* starts, const char* what) {
+    bool ok = starts[0] == 1 && starts[n] == M + 1;
+    for (int32_t i = 0; ok && i < n; i++) ok = starts[i] <= starts[i + 1];
+    if (!ok) {
+        rsem::set_last_error("%s must start at 1, end at M + 1 and never decrease", what);
+        return RSEM_ERR_INVALID;
+    }
+    return RSEM_OK;
+}
+
 constexpr int kMaxTeamDevices = 64;
 std::atomic<int> g_team_busy[kMaxTeamDevices];  // team runs in flight per device (zero-initialised)
 
@@ -558,6 +570,7 @@ int rsem_gibbs_destroy(rsem_gibbs_ctx* c) {
 
 int rsem_gibbs_set_allele_groups(rsem_gibbs_ctx* c, int32_t m_trans, const int32_t* ta) {
     RSEM_REQUIRE(c && ta && m_trans >= 1, "bad argument");
+    if (int rc = check_group_starts(c->M, m_trans, ta, "ta (the transcripts' first alleles)")) return rc;
     RSEM_HIP_TRY(hipSetDevice(c->device));
     hipFree(c->d_ta);
     c->d_ta = nullptr;
@@ -633,6 +646,7 @@ int rsem_gibbs_create(rsem_gibbs_ctx** out, int device, int32_t M, uint64_t N1, 
     RSEM_REQUIRE(N1 < 0xfffffff0ull, "N1 too large for one chain context");
     RSEM_REQUIRE(row_ptr[0] == 0 && row_ptr[N1] == nitems, "row_ptr[0] != 0 or row_ptr[N1] != nitems");
     RSEM_REQUIRE(N0 < 0x7fffffffull, "N0 does not fit the reference's int counts");
+    if (int rc = check_group_starts(M, m, grp, "grp (the genes' first transcripts)")) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
         (void)hipGetLastError();

@@ -133,6 +133,16 @@ def test_calc_ci_edge_cases():
         else:
             q1, q3 = y[q], y[3 * q]
         assert abs(orc.calc_ci(y, 0.95)[2] - (q3 - q1) / (q3 + q1)) < 1e-6
+    # the edges test_ci_gpu.py runs the kernel at, spelled out so that oracle and kernel do not merely agree with each other
+    y = np.array([7.0, 1.0, 4.0], np.float32)          # n = 3: rem == 3 with q == 0 -- hinges (x0 + x1) / 2 and (x1 + x2) / 2 of the sorted row
+    assert orc.calc_ci(y, 0.95) == (np.float32(1.0), np.float32(7.0), np.float32((5.5 - 2.5) / (5.5 + 2.5)))
+    y = np.arange(1, 10, dtype=np.float32)[::-1]       # n = 9: rem == 1, hinges x[2] and x[6]
+    assert orc.calc_ci(y, 1.0) == (np.float32(1.0), np.float32(9.0), np.float32(4.0 / 10.0))     # confidence 1: nothing outside
+    assert orc.calc_ci(y, 1e-9) == (np.float32(1.0), np.float32(1.0), np.float32(4.0 / 10.0))    # all but one outside: the lowest run
+    y = np.array([3, 3, 5, 5, 5, 8, 9, 9, 9], np.float32)
+    assert orc.calc_ci(y, 1e-9)[:2] == (3.0, 3.0) and orc.calc_ci(y, 1.0)[:2] == (3.0, 9.0)
+    y = np.arange(1, 402, dtype=np.float32)            # n = 401, confidence 0.5: 200 may lie outside, the first window of 201 wins
+    assert orc.calc_ci(y, 0.5) == (np.float32(1.0), np.float32(201.0), np.float32(np.float32(200.0) / np.float32(402.0)))
 
 
 def test_philox_known_answers(tmp_path):

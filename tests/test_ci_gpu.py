@@ -46,7 +46,10 @@ def test_intervals_bit_exact_on_reference_rows(name):
     assert ["%.6g" % v for v in cqv] == per_target[2]
 
 
-@pytest.mark.parametrize("n,conf", [(1, 0.95), (2, 0.95), (4, 0.5), (5, 0.95), (6, 0.9), (7, 0.95), (400, 0.95), (2000, 0.99), (50000, 0.95)])
+# (n = 3: the only n whose rem == 3 hinges use q == 0; confidence 1.0: no sample may lie outside; 1e-9: all but one may; 401: rem == 1.
+# What the oracle gives at these edges is spelled out in test_ci_cpu.test_calc_ci_edge_cases.)
+@pytest.mark.parametrize("n,conf", [(1, 0.95), (2, 0.95), (4, 0.5), (5, 0.95), (6, 0.9), (7, 0.95), (400, 0.95), (2000, 0.99), (50000, 0.95),
+                                    (3, 0.95), (9, 1.0), (9, 1e-9), (401, 0.5)])
 def test_intervals_bit_exact_random_rows(n, conf):
     rng = np.random.default_rng(n)
     rows = rng.gamma(0.7, 3.0, size=(37, n)).astype(np.float32)

@@ -219,9 +219,14 @@ def test_chain_groups_reduce_over_local_comm():
     d = _load("pe_q")
     seeds = capi().gibbs_chain_seeds(17, 4)
     ns = [5, 5, 4, 4]
+    # allele groups over the transcripts (the fixture has none of its own): singletons, pairs and triples
+    ta = np.unique(np.append(np.cumsum(np.tile([1, 2, 1, 3], d["M"]))[:d["M"]].clip(max=d["M"]) + 1, [1, d["M"] + 1])).astype(np.int32)
+    assert ta[0] == 1 and ta[-1] == d["M"] + 1 and set(np.diff(ta)) >= {1, 2, 3}
     ctx = _ctx(d)
-    cvs, acc, _, _ = ctx.run_chains(capi().GIBBS_EXACT, seeds, 4, ns, 1)
+    ctx.set_allele_groups(ta)
+    cvs, acc, trans, _ = ctx.run_chains(capi().GIBBS_EXACT, seeds, 4, ns, 1)
     ctx.close()
+    assert trans.any()
     comms = capi().Comm.create_local([0, 0])
     assert [c.rank for c in comms] == [0, 1] and comms[0].world == 2
     out = [None, None]
@@ -229,6 +234,7 @@ def test_chain_groups_reduce_over_local_comm():
     def group(w):
         g = _ctx(d)
         g.set_comm(comms[w])
+        g.set_allele_groups(ta)
         mine = list(range(w, 4, 2))
         out[w] = g.run_chains(capi().GIBBS_EXACT, seeds[mine], 4, [ns[k] for k in mine], 1)
         g.close()
@@ -243,6 +249,7 @@ def test_chain_groups_reduce_over_local_comm():
         assert np.allclose(a, b, rtol=1e-12, atol=1e-9)
     assert np.array_equal(out[0][0][0], cvs[0]) and np.array_equal(out[0][0][1], cvs[2])
     assert np.array_equal(out[1][0][0], cvs[1]) and np.array_equal(out[1][0][1], cvs[3])
+    assert np.array_equal(out[0][2], trans)  # sums of squared integers: the reduce cannot change them
 
 
 def test_parallel_sampler_invariants_and_determinism():
