@@ -417,6 +417,35 @@ int rsem_ci_intervals(int device, int64_t nrows, int32_t nSamples, const float* 
  * RSEM_CI_BATCH_KEYS (a whole number from nSamples to 2^30; anything else: RSEM_ERR_INVALID), read at every call, replaces
  * the 2^30 (a test knob: the results do not depend on it). */
 
+/* ---- shared k-mers (rsem-for-ebseq-calculate-clustering-info) ----------------------------------------------
+ * Replaces the sort-and-count of EBSeq/calcClusteringInfo.cpp:101-130.  codes: the transcripts' bases one after the other, one
+ * byte per base, 0 .. 4 = A C G T N (N is an ordinary fifth letter); transcript t is codes[seq_off[t] .. seq_off[t+1]).
+ * shared[t]: the number of k-mer start positions of transcript t whose k-mer also occurs in at least one OTHER transcript (a
+ * k-mer repeated only inside one transcript counts nothing; one that is repeated inside and occurs elsewhere counts every one of
+ * its positions).  Integer arithmetic: the result does not depend on any order.  Needs no context.
+ * Checked before the device is touched (RSEM_ERR_INVALID): k >= 1, seq_off[0] = 0 and never decreasing, no transcript of 2^32
+ * bases, every code <= 4.  Where no transcript is as long as k the answer is all zeros and the device is not touched either;
+ * otherwise k above 32768 is refused (RSEM_ERR_INVALID).
+ * Keys, sort values and their double buffers take 24 bytes per k-mer (32 once the bases and one separator per transcript pass
+ * 2^32): the library sorts back and forth between the two halves, and its own temporary storage, asked of it for the size in
+ * question, is counted on top.  Where that exceeds the free device memory less a margin, the k-mers are cut into batches by the value of their first
+ * min(k, 8) bases: whole buckets in ascending order while they stay within the budget, a bucket above the budget a batch of its
+ * own; a batch that does not fit the device, or holds 2^31 k-mers, fails with RSEM_ERR_NOMEM before anything is sorted.  The
+ * environment variable RSEM_KMER_BATCH_ITEMS (a whole number >= 1; anything else: RSEM_ERR_INVALID), read at every call, replaces
+ * the budget (a test knob: the results do not depend on it, n_batches does).  RSEM_KMER_WIDE_VALUES = 1 (0 or 1; anything else:
+ * RSEM_ERR_INVALID) sorts by 64-bit positions whatever the length (a test knob: small inputs through the path of 2^32 bases). */
+typedef struct rsem_kmer_info {
+    uint64_t n_kmers, n_groups;   /* k-mer start positions; distinct k-mers */
+    int32_t n_batches, n_chunks;  /* n_chunks = ceil(k / 27): sorts per batch */
+    uint64_t batch_items;         /* the budget in force */
+    uint64_t max_batch_items;     /* the largest batch */
+    uint64_t batch_bytes;         /* device bytes of the batch buffers: the halves of keys and values and the library's temporary storage */
+    double upload_ms;             /* bases and offsets to the device */
+    double kernel_ms;             /* from there to the last counter: kernels, library sorts and scans, the batches' hand-offs */
+} rsem_kmer_info;
+int rsem_kmer_shared_counts(int device, int32_t M, const uint64_t* seq_off /* M+1 */, const uint8_t* codes, int32_t k,
+                            uint32_t* shared /* M */, rsem_kmer_info* info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,12 @@ class GibbsDiagSummary(C.Structure):
                 ("max_rhat", C.c_double), ("min_ess", C.c_double), ("upload_ms", C.c_double), ("kernel_ms", C.c_double)]
 
 
+class KmerInfo(C.Structure):
+    _fields_ = [("n_kmers", C.c_uint64), ("n_groups", C.c_uint64), ("n_batches", C.c_int32), ("n_chunks", C.c_int32),
+                ("batch_items", C.c_uint64), ("max_batch_items", C.c_uint64), ("batch_bytes", C.c_uint64),
+                ("upload_ms", C.c_double), ("kernel_ms", C.c_double)]
+
+
 class EmProfile(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("estep_ms_sum", C.c_double), ("estep_launches", C.c_int32),
                 ("rounds", C.c_int32), ("algorithmic_bytes_per_round", C.c_uint64)]
@@ -110,6 +116,7 @@ def lib():
                                                 _f32p, _f32p, _f32p, _f32p, vp, vp, vp]
         L.rsem_ci_sample.argtypes = [ci, i32, i32, i32, _i32p, _f64p, _f64p, dbl, u64, _f32p, _f32p]
         L.rsem_ci_intervals.argtypes = [ci, C.c_int64, i32, _f32p, dbl, _f32p, _f32p, _f32p]
+        L.rsem_kmer_shared_counts.argtypes = [ci, i32, _u64p, vp, i32, _u32p, vp]
         _lib = L
     return _lib
 
@@ -389,6 +396,19 @@ def gibbs_diagnose(cvs, device=0):
     _check(lib().rsem_gibbs_diagnose(device, M1 - 1, n, _ptr(ns), C.cast(ptrs, C.c_void_p), _ptr(mean), _ptr(sd), _ptr(rhat), _ptr(ess),
                                      _ptr(lag), C.addressof(sm)))
     return mean, sd, rhat, ess, lag, {k: getattr(sm, k) for k, _ in GibbsDiagSummary._fields_}
+
+
+def kmer_shared_counts(seq_off, codes, k, device=0):
+    """rsem_kmer_shared_counts: per transcript the number of k-mer start positions whose k-mer also occurs in another transcript.
+    codes: uint8 0 .. 4 (A C G T N), transcript t = codes[seq_off[t]:seq_off[t+1]].  Returns (shared uint32[M], info dict)."""
+    seq_off = np.ascontiguousarray(seq_off, np.uint64)
+    codes = np.ascontiguousarray(codes, np.uint8)
+    M = len(seq_off) - 1
+    assert M >= 0 and (M == 0 or int(seq_off[-1]) <= codes.size)
+    shared = np.zeros(max(M, 1), np.uint32)
+    info = KmerInfo()
+    _check(lib().rsem_kmer_shared_counts(device, M, seq_off, _ptr(codes), int(k), shared, C.addressof(info)))
+    return shared[:M], {f: getattr(info, f) for f, _ in KmerInfo._fields_}
 
 
 def ci_intervals(rows, confidence, device=0):
