@@ -446,6 +446,35 @@ typedef struct rsem_kmer_info {
 int rsem_kmer_shared_counts(int device, int32_t M, const uint64_t* seq_off /* M+1 */, const uint8_t* codes, int32_t k,
                             uint32_t* shared /* M */, rsem_kmer_info* info /* may be NULL */);
 
+/* ---- per-base read depth (rsem-bam2wig, rsem-bam2readdepth) -------------------------------------------------
+ * Replaces the loop of wiggle.cpp:16-37 (`read_depth[pos] += w` once per aligned base, on one thread).  Block i covers the bases
+ * start[i] .. start[i] + len[i] - 1 with the weight w[i]; the blocks are given in record order.  depth[b] becomes the FOLD
+ * ((depth[b] + w[i1]) + w[i2]) + ..., over the blocks i1 < i2 < ... that cover base b, in that order, continued from the value
+ * passed in -- bit for bit what the reference's loop leaves, whose sums depend on the order of their additions.  No floating-point
+ * atomic, prefix sum or tree takes part.  Needs no context.
+ * Checked before the device is touched (RSEM_ERR_INVALID): start[i] + len[i] <= n_bases for every block, without overflow.
+ * n_blocks == 0 or n_bases == 0 leaves depth as it is and does not touch the device; neither do blocks that all have len 0.
+ * The bases are cut into tiles of 512; a block makes one entry per tile it touches; a stable radix sort on the tile groups the entries
+ * and keeps the blocks' order inside a tile; one workgroup per touched tile folds.  The blocks go through in batches, in their order:
+ * whole blocks while their items (a block's entries, 1 for a block without bases) stay within the budget of 2^26, a block above the
+ * budget a batch of its own.  depth stays on the device from the first batch to the last: n_bases doubles, 28 bytes per block and
+ * 28 per entry of the largest batch and the library's temporary storage have to fit (RSEM_ERR_NOMEM before anything is allocated);
+ * a caller with more bases than that calls once per stretch of them.  The environment variable RSEM_DEPTH_BATCH_ITEMS (a whole
+ * number >= 1; anything else: RSEM_ERR_INVALID), read at every call, replaces the budget (a test knob: the results do not depend
+ * on it, n_batches does). */
+typedef struct rsem_depth_info {
+    uint64_t n_entries;        /* (block, tile) pairs */
+    uint64_t n_tiles_touched;  /* summed over the batches: a tile that two batches touch counts twice */
+    int32_t n_batches;
+    int32_t n_launches;        /* kernels and library calls: seven per batch that has entries, whatever the blocks are */
+    uint64_t batch_items;      /* the budget in force */
+    uint64_t device_bytes;     /* allocated for the call */
+    double upload_ms;          /* depth and the batches' blocks to the device */
+    double kernel_ms;          /* the batches' kernels, sorts and scans */
+} rsem_depth_info;
+int rsem_depth_accumulate(int device, uint64_t n_bases, uint64_t n_blocks, const uint64_t* start, const uint32_t* len, const double* w,
+                          double* depth /* n_bases, in and out */, rsem_depth_info* info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,11 @@ class KmerInfo(C.Structure):
                 ("upload_ms", C.c_double), ("kernel_ms", C.c_double)]
 
 
+class DepthInfo(C.Structure):
+    _fields_ = [("n_entries", C.c_uint64), ("n_tiles_touched", C.c_uint64), ("n_batches", C.c_int32), ("n_launches", C.c_int32),
+                ("batch_items", C.c_uint64), ("device_bytes", C.c_uint64), ("upload_ms", C.c_double), ("kernel_ms", C.c_double)]
+
+
 class EmProfile(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("estep_ms_sum", C.c_double), ("estep_launches", C.c_int32),
                 ("rounds", C.c_int32), ("algorithmic_bytes_per_round", C.c_uint64)]
@@ -117,6 +122,7 @@ def lib():
         L.rsem_ci_sample.argtypes = [ci, i32, i32, i32, _i32p, _f64p, _f64p, dbl, u64, _f32p, _f32p]
         L.rsem_ci_intervals.argtypes = [ci, C.c_int64, i32, _f32p, dbl, _f32p, _f32p, _f32p]
         L.rsem_kmer_shared_counts.argtypes = [ci, i32, _u64p, vp, i32, _u32p, vp]
+        L.rsem_depth_accumulate.argtypes = [ci, u64, u64, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -409,6 +415,20 @@ def kmer_shared_counts(seq_off, codes, k, device=0):
     info = KmerInfo()
     _check(lib().rsem_kmer_shared_counts(device, M, seq_off, _ptr(codes), int(k), shared, C.addressof(info)))
     return shared[:M], {f: getattr(info, f) for f, _ in KmerInfo._fields_}
+
+
+def depth_accumulate(n_bases, start, length, w, depth=None, device=0):
+    """rsem_depth_accumulate: depth[b] = the fold, in block order, of w[i] over the blocks [start[i], start[i] + length[i]) that cover
+    base b, continued from `depth` (zeros where None).  Returns (depth float64[n_bases], info dict); `depth` itself is not changed."""
+    start = np.ascontiguousarray(start, np.uint64)
+    length = np.ascontiguousarray(length, np.uint32)
+    w = np.ascontiguousarray(w, np.float64)
+    assert start.shape == length.shape == w.shape and start.ndim == 1
+    out = np.zeros(int(n_bases), np.float64) if depth is None else np.array(depth, np.float64, order="C")
+    assert out.shape == (int(n_bases),)
+    info = DepthInfo()
+    _check(lib().rsem_depth_accumulate(device, int(n_bases), len(start), _ptr(start), _ptr(length), _ptr(w), _ptr(out), C.addressof(info)))
+    return out, {f: getattr(info, f) for f, _ in DepthInfo._fields_}
 
 
 def ci_intervals(rows, confidence, device=0):
