@@ -7,7 +7,10 @@
 // positional split of the products and count updates (reads longer than 128 bases take a second pass), the DPP
 // reductions, reads of different lengths / alignment counts side by side in one wave.  Never part of the product.
 //
-//   model_emu <model_type 0..3> <seed> <estRSPD 0|1> <has_mld 0|1 (single-end only)>      exit 0 = all tables agree
+//   model_emu <model_type 0..3> <seed> <estRSPD 0|1> <has_mld 0|1 (single-end only)> [aligner_like 0|1]     exit 0 = all tables agree
+// aligner_like 1: some reads hit a transcript a second time, on other bases (an aligner's report of an internal repeat): the alignment
+// in the middle of the read -- and, in half of the reads of more than 17 alignments, the first of the second chunk -- becomes its
+// predecessor's transcript at a position 7 bases off.  The run of equal windows around it is interrupted and resumes behind it.
 // Build (tests/test_model_emu_cpu.py): hipcc -DRSEM_EMU -O1 -std=c++17 tests/model_emu.cpp -lpthread
 #include <random>
 
@@ -90,6 +93,7 @@ int main(int argc, char** argv) {
     const int type = atoi(argv[1]);
     const unsigned seed = (unsigned)atoi(argv[2]);
     const int estRSPD = atoi(argv[3]), has_mld = atoi(argv[4]);
+    const bool aligner_like = argc > 5 && atoi(argv[5]) != 0;
     const bool q = type == 1 || type == 3, pe = type >= 2;
     std::mt19937_64 rng(seed);
     auto irand = [&](int a, int b) { return (int)(rng() % (uint64_t)(b - a + 1)) + a; };
@@ -151,6 +155,16 @@ int main(int argc, char** argv) {
             sid_signed.push_back(dir ? -t : t);
             pos.push_back(p);
             insertL.push_back(insert);
+        }
+        if (aligner_like && nal >= 3 && i % 3 != 1) {  // (no random numbers drawn: everything else is the data of aligner_like 0)
+            const size_t r0 = (size_t)row_ptr.back();
+            auto second_hit = [&](int k) {  // alignment k: the transcript of k - 1 once more, 7 bases off (inside it: p0 + 2 + insert < 400)
+                const int pp = pos[r0 + k - 1];
+                sid_signed[r0 + k] = sid_signed[r0 + k - 1];
+                pos[r0 + k] = pp >= 7 ? pp - 7 : pp + 7;
+            };
+            second_hit(nal / 2);
+            if (nal > 17 && i % 34 == 0 && nal / 2 != 15 && nal / 2 != 17) second_hit(16);
         }
         row_ptr.push_back(sid_signed.size());
         // the read's bases: the first alignment's window with errors
@@ -386,8 +400,17 @@ int main(int argc, char** argv) {
         }
     }
     // how much of the special cases the data holds
-    int long_rows = 0, shared = 0, contd = 0;
+    // resumed: reads in which a run of equal windows is interrupted and resumed -- an alignment whose window is not its predecessor's
+    // but the one before that; twice: reads that hit a transcript at two positions
+    int long_rows = 0, shared = 0, contd = 0, resumed = 0, twice = 0, second_at_16 = 0;
     for (uint64_t i = 0; i < N1; i++) {
+        bool res = false, tw = false;
+        for (uint64_t j = row_ptr[i] + 1; j < row_ptr[i + 1]; j++) {
+            if (j >= row_ptr[i] + 2 && !lq[i] && !(same_prev[j] & 1) && !memcmp(window(j, 0, 0), window(j - 2, 0, 0), (size_t)rlen[0][i])) res = true;
+            if (sid_signed[j] == sid_signed[j - 1] && pos[j] != pos[j - 1]) { tw = true; if (j - row_ptr[i] == 16) ++second_at_16; }
+        }
+        resumed += res;
+        twice += tw;
         if (row_ptr[i + 1] - row_ptr[i] > 16) ++long_rows;
         for (uint64_t j = row_ptr[i]; j < row_ptr[i + 1]; j++) {
             if (same_prev[j] & 3) ++shared;
@@ -396,6 +419,9 @@ int main(int argc, char** argv) {
     }
     printf("reads %llu alignments %llu, reads with > 16 alignments %d, alignments sharing a window with their predecessor %d, of them first of a chunk %d\n",
            (unsigned long long)N1, (unsigned long long)nnz, long_rows, shared, contd);
+    printf("reads that hit a transcript at two positions %d (at alignment 16: %d), reads whose run of equal windows is interrupted and resumed %d\n",
+           twice, second_at_16, resumed);
     if (!long_rows || !shared || !contd) { printf("test data lacks a special case\n"); ++bad; }
+    if (aligner_like && (!resumed || !second_at_16 || twice * 20 < (int)N1)) { printf("test data lacks a special case of aligner_like\n"); ++bad; }
     return bad ? 1 : 0;
 }

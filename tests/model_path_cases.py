@@ -10,7 +10,11 @@ Paths (model_block.hpp):
      table indices >= kGldLds = 1024 (likewise);
   4  plane output for reads of 17..256 alignments, CSR only for reads with more than 256;
   5  reads of different lengths side by side, N bases, low-quality reads (shorter than the seed length 25), probF 0 / 1, RSPD
-     estimation, a mate-length distribution, omitted transcripts.
+     estimation, a mate-length distribution, omitted transcripts;
+  6  reads as an aligner reports them (the repeat_ cases; gen_temp --near-repeat / --shuffle-alignments): a transcript hit at two
+     positions by one read, on equal bases or on bases that differ in a few places, alignments in any order -- runs of equal
+     windows (same_prev) between two alignments of ONE transcript, runs that are interrupted and resume, a second hit as the
+     first alignment of a chunk.
 
 Every case: positional arguments of tools/gen_temp.cpp (reads, M, read type, read_len, isoforms per gene) + named options.
 20 000 reads each (19 000 alignable): the reference binary finishes a case in 5-20 s with -p 4 (over_256, 271 alignments per
@@ -54,6 +58,14 @@ CASES = {
     "stranded_fwd_rspd_omit": dict(rt=3, n=20000, M=2000, L=75, iso="17-40", opts=["--probF", "1", "--est-rspd", "1", "--omit", "60"], planes0=True),
     # single-end reads with a fragment length distribution (the loop over fragment lengths and a mate-length table), with path 1
     "se_mld": dict(rt=1, n=20000, M=2000, L=100, iso="17-40", opts=["--len", "50-100", "--se-frag", "180,40", "--frag-range", "1-300"], planes0=True),
+    # path 6.  Short genes and reads of 50 bases: one fragment in five lies inside one copy of its gene's 200-base repeat.
+    # expect: the least share of the reads with each feature (assert_path / assert_path_ofg); at_chunk: a second hit at entry 16 or 32
+    "repeat_se_q": dict(rt=1, n=20000, M=2000, L=50, iso="2-9", opts=["--gene-len", "1500-2000", "--near-repeat", "200:0.02", "--shuffle-alignments"],
+                        planes0=False, expect=dict(repeat=0.05, not_ascending=0.05, resumed=0.01)),
+    "repeat_pe": dict(rt=3, n=20000, M=2000, L=50, iso="2-9", opts=["--gene-len", "1500-2000", "--pe-frag", "120,20,200", "--near-repeat", "200:0"],
+                      planes0=False, expect=dict(repeat=0.05)),
+    "repeat_long": dict(rt=1, n=20000, M=2000, L=50, iso="17-40", opts=["--gene-len", "1500-2000", "--near-repeat", "200:0.02", "--shuffle-alignments"],
+                        planes0=True, expect=dict(repeat=0.05, not_ascending=0.05, resumed=0.01, at_chunk=True)),
 }
 
 
@@ -119,6 +131,7 @@ def parse_inputs(case, d):
         nal = np.zeros(N1, np.int64)
         frag = np.zeros(N1, np.int64)
         strands, sids = set(), set()
+        alns = [] if "expect" in case else None   # per read: (transcript ids, positions) in file order
         for i, line in enumerate(f):
             t = line.split()
             k = int(t[0])
@@ -129,6 +142,8 @@ def parse_inputs(case, d):
             sids.update(abs(x) for x in ids)
             if pe:
                 frag[i] = int(t[3])
+            if alns is not None:
+                alns.append((np.array(ids, np.int64), np.array(t[2::w], np.int64)))
     assert i + 1 == N1 and int(nal.sum()) == nHits
     mates = [_read_lengths(os.path.join(d, "temp", r), case["rt"] in (1, 3)) for r in read_files(case)]
     assert all(len(m[0]) == N1 for m in mates)
@@ -138,8 +153,35 @@ def parse_inputs(case, d):
         omit = [int(x) for x in f.read().split()]
     with open(os.path.join(d, "temp", "s.mparams")) as f:
         mparams = f.read().split()
-    return dict(N1=N1, nal=nal, lens=lens, maxlen=lens.max(0), minlen=lens.min(0), has_n=has_n, frag=frag, strands=strands, sids=sids, omit=omit,
-                mparams=mparams)
+    P = dict(N1=N1, nal=nal, lens=lens, maxlen=lens.max(0), minlen=lens.min(0), has_n=has_n, frag=frag, strands=strands, sids=sids, omit=omit,
+             mparams=mparams)
+    if alns is not None:
+        P["aligner_like"] = _aligner_like_counts(case, d, alns, lens[0])
+    return P
+
+
+def _aligner_like_counts(case, d, alns, len1):
+    """Reads with: a transcript hit twice (repeat); ids not ascending; a run of equal windows that is interrupted and resumes -- an
+    alignment whose window holds other bases than its predecessor's and the same as the one before that (single-end: the window
+    is the read's length of the transcript's strand at the position); a second hit of a transcript as entry 16 or 32 (at_chunk)."""
+    with open(os.path.join(d, "ref.seq")) as f:
+        lines = f.read().split("\n")
+    seqs = [""] + lines[2::4][:case["M"]]            # per transcript: 'len len', name, bases, mask words
+    assert len(seqs) == case["M"] + 1 and all(set(s) <= set("ACGTN") for s in seqs[1:20])
+    c = dict(repeat=0, not_ascending=0, resumed=0, at_chunk=0)
+    for i, (ids, pos) in enumerate(alns):
+        t = np.abs(ids)
+        if len(np.unique(t)) == len(t) and not np.any(t[1:] < t[:-1]):
+            continue
+        c["repeat"] += len(np.unique(t)) < len(t)
+        c["not_ascending"] += bool(np.any(t[1:] < t[:-1]))
+        c["at_chunk"] += any(len(t) > e and t[e] in t[:e] for e in (K_GRP, 2 * K_GRP))
+        if case["rt"] < 2:
+            n = int(len1[i])
+            win = [seqs[a][p:p + n] if s > 0 else seqs[a][len(seqs[a]) - p - n:len(seqs[a]) - p] for s, a, p in zip(ids.tolist(), t.tolist(), pos.tolist())]
+            assert all(len(x) == n for x in win)
+            c["resumed"] += any(win[j] != win[j - 1] and win[j] == win[j - 2] for j in range(2, len(win)))
+    return c
 
 
 def assert_path(name, P):
@@ -180,3 +222,33 @@ def assert_path(name, P):
         assert float(P["mparams"][7]) > 0 and len(set(maxlen.tolist())) > 1
     else:
         assert P["mparams"][7] == "-1"
+    if name.startswith("repeat_"):
+        c = P["aligner_like"]
+        print("aligner_like %s: of %d reads %s" % (name, N1, " ".join("%s=%d" % kv for kv in c.items())))
+        for k, least in case["expect"].items():
+            assert c[k] >= (1 if least is True else least * N1), (name, k, c[k], least)
+        if name == "repeat_long":
+            assert frac(nal > K_GRP) >= 0.20 and nal.max() <= K_PLANE_MAX, (name, frac(nal > K_GRP), int(nal.max()))
+
+
+def assert_path_ofg(name, ofg):
+    """... and from the reference's .ofg (M, N0, row_ptr, ids, values): among the reads with two entries of one transcript at least
+    half have the two within a factor of 100 of each other -- the second hit then takes a share of the read that the model's
+    statistics depend on, and a kernel that lost or doubled it would show in every table."""
+    if not name.startswith("repeat_"):
+        return
+    _, _, rp, sid, val = ofg
+    rp = rp.astype(np.int64)
+    both = close = 0
+    for i in range(len(rp) - 1):
+        s, v = sid[rp[i]:rp[i + 1]], val[rp[i]:rp[i + 1]]
+        if len(np.unique(s)) == len(s):
+            continue
+        both += 1
+        o = np.argsort(s, kind="stable")
+        s, v = s[o], v[o]
+        pair = np.flatnonzero(s[1:] == s[:-1])
+        ratio = np.maximum(v[pair], v[pair + 1]) / np.minimum(v[pair], v[pair + 1])
+        close += bool(np.any(ratio <= 100.0))
+    print("aligner_like %s: .ofg rows with two entries of one transcript %d, of them within a factor of 100 %d" % (name, both, close))
+    assert both >= 0.05 * (len(rp) - 1) and 2 * close >= both, (name, both, close)

@@ -13,6 +13,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import aligner_like as al
 from oracle import pyoracle as orc
 from tools.q32_ref import quantize_q32
 
@@ -47,7 +48,7 @@ def emulators(tmp_path_factory):
     return out
 
 
-def _data(seed, M=500, n=1200, maxlen=60):
+def _data(seed, M=500, n=1200, maxlen=60, aligner_like=False):
     rng = np.random.default_rng(seed)
     lens = np.concatenate([np.arange(1, 257), rng.integers(1, maxlen, n)]).astype(np.int64)  # every length once, then a bulk
     rng.shuffle(lens)
@@ -63,6 +64,8 @@ def _data(seed, M=500, n=1200, maxlen=60):
     theta[rng.random(M + 1) < 0.1] = 1e-310   # theta * conprb under the 1e-300 clamp
     theta[0] = 0.3
     theta /= theta.sum()
+    if aligner_like:   # repeated ids and ids out of order: reads of one (length, start) no longer share a tuple, often in a later plane only
+        sid = al.aligner_like(rp, sid, seed + 100)
     return M, rp, sid, cp, ncp, theta
 
 
@@ -82,8 +85,11 @@ def _run(exe, M, rp, sid, cp, ncp, theta_in, N0=0.0, T=4, policy=0, q32=0, range
         shutil.rmtree(d, ignore_errors=True)
 
 
-def _check(exe, seed=1, **kw):
-    M, rp, sid, cp, ncp, theta = _data(seed)
+def _check(exe, seed=1, aligner_like=False, **kw):
+    M, rp, sid, cp, ncp, theta = _data(seed, aligner_like=aligner_like)
+    if aligner_like:
+        al.assert_on_path(al.describe(rp, sid, window=kw.get("window") or al.WINDOW), repeat=0.05, all_same=0.05, not_ascending=0.05,
+                          same_plane=0.05, same_lane=0.05, **(dict(far_repeat=0.05) if kw.get("window") == 16 else {}))   # (most reads are shorter than the other windows)
     vals = quantize_q32(rp, cp, kw.get("range_bits", 8))[0] if kw.get("q32") else cp
     N0, theta_in = 0.0, theta
     if kw.get("from_counts"):  # theta_i = (c_i + [i = 0] (noise + N0)) / (N0 + reads with a non-zero normaliser), EM.cpp:392-398
@@ -113,18 +119,23 @@ CASES = [dict(), dict(from_counts=1), dict(window=64), dict(q32=1), dict(q32=1, 
          dict(policy=3, window=64), dict(policy=3, window=16, T=3, seed=2), dict(policy=3, window=256, T=8, seed=4)]
 
 
-@pytest.mark.parametrize("kw", CASES, ids=lambda k: "-".join("%s%s" % kv for kv in sorted(k.items())) or "plain")
+def _both(cases):
+    """Every case as it is, then again on the aligner-like input (tests/aligner_like.py)."""
+    return cases + [dict(kw, aligner_like=True) for kw in cases]
+
+
+@pytest.mark.parametrize("kw", _both(CASES), ids=lambda k: "-".join("%s%s" % kv for kv in sorted(k.items())) or "plain")
 def test_kernel_body_as_built_for_the_product(emulators, kw):
     _check(emulators["product"], **kw)
 
 
-@pytest.mark.parametrize("kw", CASES[:4] + [dict(q32=1, from_counts=1, T=5, seed=2), dict(T=1, window=16, seed=3), dict(policy=1, window=16, from_counts=1, T=3, seed=2)],
+@pytest.mark.parametrize("kw", _both(CASES[:4] + [dict(q32=1, from_counts=1, T=5, seed=2), dict(T=1, window=16, seed=3), dict(policy=1, window=16, from_counts=1, T=3, seed=2)]),
                          ids=lambda k: "-".join("%s%s" % kv for kv in sorted(k.items())) or "plain")
 def test_other_prefetch_depths(emulators, kw):
     _check(emulators["variants"], **kw)
 
 
-@pytest.mark.parametrize("kw", [dict(window=64), dict(policy=1, window=16, from_counts=1, T=3, seed=2), dict(q32=1, window=64)],
+@pytest.mark.parametrize("kw", _both([dict(window=64), dict(policy=1, window=16, from_counts=1, T=3, seed=2), dict(q32=1, window=64)]),
                          ids=lambda k: "-".join("%s%s" % kv for kv in sorted(k.items())))
 def test_far_units_without_the_queue(emulators, kw, monkeypatch):
     """The units with ids outside their window take the far-queue instantiation (a lane's partial counts for such ids wait in LDS and
@@ -134,7 +145,7 @@ def test_far_units_without_the_queue(emulators, kw, monkeypatch):
     _check(emulators["product"], **kw)
 
 
-@pytest.mark.parametrize("kw", [dict(policy=2, window=64), dict(T=1, window=16, seed=3)] + ([dict(from_counts=1), dict(q32=1)] if os.environ.get("RSEM_TSAN_ALL") else []), ids=lambda k: "-".join("%s%s" % kv for kv in sorted(k.items())))
+@pytest.mark.parametrize("kw", _both([dict(policy=2, window=64), dict(T=1, window=16, seed=3)] + ([dict(from_counts=1), dict(q32=1)] if os.environ.get("RSEM_TSAN_ALL") else [])), ids=lambda k: "-".join("%s%s" % kv for kv in sorted(k.items())))
 def test_no_unordered_accesses_between_lanes(emulators, kw, monkeypatch):
     """The kernel body under ThreadSanitizer (a report makes the emulator exit with 66).  The one store that overlaps on purpose --
     every lane of a split read stores the same reciprocal -- goes through RSEM_STORE_SAME (simt_macros.hpp)."""

@@ -12,6 +12,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import aligner_like as al
 from oracle import pyoracle as orc
 from tools.q32_ref import quantize_q32
 
@@ -63,7 +64,7 @@ def test_class_table_and_index_helpers(emulators):
     assert total / sum(range(1, 257)) < 1 + 1 / 16
 
 
-def _lens_data(lens, M, seed, unique):
+def _lens_data(lens, M, seed, unique, aligner_like=False):
     rng = np.random.default_rng(seed)
     lens = np.asarray(lens, np.int64)
     rp = np.zeros(len(lens) + 1, np.uint64)
@@ -83,6 +84,9 @@ def _lens_data(lens, M, seed, unique):
     theta[rng.random(M + 1) < 0.1] = 1e-310   # theta * conprb under the 1e-300 clamp
     theta[0] = 0.3
     theta /= theta.sum()
+    if aligner_like:   # repeated ids, ids out of order (tests/aligner_like.py)
+        sid = al.aligner_like(rp, sid, seed + 100)
+        al.assert_on_path(al.describe(rp, sid), repeat=0.05, all_same=0.05, not_ascending=0.05, same_plane=0.05, same_lane=0.05)
     return M, rp, sid, cp, ncp, theta
 
 
@@ -114,15 +118,15 @@ def _run(exe, M, rp, sid, cp, ncp, theta, T=4, min_units=-1, q32=0, range_bits=8
         shutil.rmtree(d, ignore_errors=True)
 
 
-def _mixed(seed, maxlen=60, n=3000):
+def _mixed(seed, maxlen=60, n=3000, aligner_like=False):
     rng = np.random.default_rng(seed)
     lens = np.concatenate([np.arange(1, 257), rng.integers(1, maxlen, n)])  # every length once (thin classes), then a bulk (thick ones)
     rng.shuffle(lens)
-    return _lens_data(lens, 2000, seed, unique=False)
+    return _lens_data(lens, 2000, seed, unique=False, aligner_like=aligner_like)
 
 
-def _against_oracle(exe, seed, **kw):
-    M, rp, sid, cp, ncp, theta = _mixed(seed)
+def _against_oracle(exe, seed, aligner_like=False, **kw):
+    M, rp, sid, cp, ncp, theta = _mixed(seed, aligner_like=aligner_like)
     vals = quantize_q32(rp, cp, kw.get("range_bits", 8))[0] if kw.get("q32") else cp
     oc = orc.em_estep(M, rp, sid, vals, ncp, theta)
     counts, noise, neff, info = _run(exe, M, rp, sid, cp, ncp, theta, **kw)
@@ -144,6 +148,14 @@ def test_every_class_against_the_oracle(emulators):
     off = _run(emulators["product"], *_mixed(1), min_units=0)[3]
     assert not any(s[3] for s in off["shapes"]) and off["mask"] == 0
     assert info["entries"] < off["entries"] and info["entries"] < 1.05 * nnz + 64 * 4 * len(info["shapes"])
+
+
+@pytest.mark.parametrize("q32", [0, 1], ids=["f64", "q32"])
+def test_every_class_on_aligner_like_input(emulators, q32):
+    """The classes on, every length 1..256, on reads with repeated ids and ids out of order: a compacted last plane holds a copy of an id
+    of an earlier plane, or of another lane of its own."""
+    info, _ = _against_oracle(emulators["product"], 1, aligner_like=True, min_units=-1, q32=q32)
+    assert any(fmt == q32 and cut for fmt, lg, K, cut, rows in info["shapes"])
 
 
 def test_thin_classes_fold_back(emulators):
@@ -191,7 +203,8 @@ def test_bit_for_bit_against_the_full_layout(emulators, lens, q32):
     assert np.allclose(on[0][1:], oc[1:], rtol=1e-9, atol=0.0)
 
 
-@pytest.mark.parametrize("kw", [dict(min_units=-1, T=1), dict(min_units=1, T=2, q32=1)], ids=["f64-all", "q32-threshold"])
+@pytest.mark.parametrize("kw", [dict(min_units=-1, T=1), dict(min_units=1, T=2, q32=1), dict(min_units=-1, T=1, aligner_like=True)],
+                         ids=["f64-all", "q32-threshold", "f64-all-aligner_like"])
 def test_no_unordered_accesses_between_lanes(emulators, kw, monkeypatch):
     """The kernel body on the short classes under ThreadSanitizer (a report makes the emulator exit with 66)."""
     if emulators["tsan"] is None:
@@ -199,7 +212,8 @@ def test_no_unordered_accesses_between_lanes(emulators, kw, monkeypatch):
     monkeypatch.setenv("TSAN_OPTIONS", "halt_on_error=0 exitcode=66")
     rng = np.random.default_rng(5)
     lens = np.concatenate([np.arange(5, 257, 3), rng.integers(1, 40, 400)])
-    M, rp, sid, cp, ncp, theta = _lens_data(lens, 2000, 5, unique=False)
+    kw = dict(kw)
+    M, rp, sid, cp, ncp, theta = _lens_data(lens, 2000, 5, unique=False, aligner_like=kw.pop("aligner_like", False))
     vals = quantize_q32(rp, cp, 8)[0] if kw.get("q32") else cp
     oc = orc.em_estep(M, rp, sid, vals, ncp, theta)
     counts, noise, neff, info = _run(emulators["tsan"], M, rp, sid, cp, ncp, theta, **kw)

@@ -12,6 +12,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import aligner_like as al
 from oracle import pyoracle as orc
 from tools.q32_ref import quantize_q32
 from tools.synth_data import make_em_workload
@@ -41,7 +42,7 @@ def emulators(tmp_path_factory):
     return out
 
 
-def _lens_data(lens, M, seed, unique, per_tuple=40):
+def _lens_data(lens, M, seed, unique, per_tuple=40, aligner_like=False):
     rng = np.random.default_rng(seed)
     lens = np.asarray(lens, np.int64)
     rp = np.zeros(len(lens) + 1, np.uint64)
@@ -61,6 +62,9 @@ def _lens_data(lens, M, seed, unique, per_tuple=40):
     theta[rng.random(M + 1) < 0.1] = 1e-310   # theta * conprb under the 1e-300 clamp
     theta[0] = 0.3
     theta /= theta.sum()
+    if aligner_like:   # repeated ids, ids out of order (tests/aligner_like.py): tuples that differ in a later plane only
+        sid = al.aligner_like(rp, sid, seed + 100)
+        al.assert_on_path(al.describe(rp, sid), repeat=0.05, all_same=0.05, not_ascending=0.05, same_plane=0.05, same_lane=0.05)
     return M, rp, sid, cp, ncp, theta
 
 
@@ -96,10 +100,10 @@ def _run(exe, M, rp, sid, cp, ncp, theta_in, N0=0.0, T=4, min_units=0, q32=0, ra
 
 # ---- 1. what the list holds -----------------------------------------------------------------------------------------------------------
 
-def _sweep():
+def _sweep(aligner_like=False):
     """Every row length 1..256, three reads per length, two of them with the same tuple."""
     lens = np.repeat(np.arange(1, 257), 3)
-    return _lens_data(lens, 2000, 3, unique=False)
+    return _lens_data(lens, 2000, 3, unique=False, aligner_like=aligner_like)
 
 
 def _workload(name):
@@ -109,13 +113,13 @@ def _workload(name):
 
 @pytest.mark.parametrize("q32", [0, 1], ids=["f64", "q32"])
 @pytest.mark.parametrize("min_units", [0, -1], ids=["full", "short"])
-@pytest.mark.parametrize("name", ["sweep", "tiny", "tinyX", "small"])
+@pytest.mark.parametrize("name", ["sweep", "tiny", "tinyX", "small", "sweep-aligner_like"])
 def test_list_holds_the_ids_of_the_lanes_that_start(emulators, name, min_units, q32):
     """For every slice, lane and plane with the mask bit set the list entry is the plane entry, at plane * n + rank from the slice's
     offset; the offsets are the exclusive sums of K * popcount(mask); the total is their sum and nothing is written behind it
     (checked entry by entry in the emulator, which builds the list with start_list_count / start_list_fill_lane)."""
-    data = _sweep() if name == "sweep" else _workload(name)
-    T = {"sweep": 3, "tiny": 8, "tinyX": 8, "small": 70}[name]
+    data = _sweep(name != "sweep") if name.startswith("sweep") else _workload(name)
+    T = {"sweep": 3, "sweep-aligner_like": 3, "tiny": 8, "tinyX": 8, "small": 70}[name]
     kw = dict(T=T, min_units=min_units if name != "small" or min_units == 0 else 8, q32=q32, run=0)
     if name == "tinyX":
         kw.update(policy=3, window=64)   # split rows: their planes hold the in-window ids only
@@ -157,11 +161,11 @@ def test_byte_accounting_rule(emulators, kw):
 
 # ---- 2. the loop with the list ----------------------------------------------------------------------------------------------------------
 
-def _mixed(seed, n=1200, maxlen=60, M=500):
+def _mixed(seed, n=1200, maxlen=60, M=500, aligner_like=False):
     rng = np.random.default_rng(seed)
     lens = np.concatenate([np.arange(1, 257), rng.integers(1, maxlen, n)])   # every length once (K = 1..4, lg = 0..6), then a bulk
     rng.shuffle(lens)
-    return _lens_data(lens, M, seed, unique=False)
+    return _lens_data(lens, M, seed, unique=False, aligner_like=aligner_like)
 
 
 def _from_counts(theta):
@@ -213,10 +217,22 @@ def test_loop_with_the_list_against_the_oracle(emulators, case):
     _against_oracle(emulators["product"], _mixed(1 + len(case)), **LOOP_CASES[case])
 
 
+@pytest.mark.parametrize("case", sorted(LOOP_CASES))
+def test_loop_with_the_list_on_aligner_like_input(emulators, case):
+    """Reads of one (length, start) differ where the transform wrote a repeat or moved ids, often in a later plane only: a lane that
+    missed such a start would go on with the ids of the read before."""
+    _against_oracle(emulators["product"], _mixed(1 + len(case), aligner_like=True), **LOOP_CASES[case])
+
+
 @pytest.mark.parametrize("case", ["plain", "from-counts", "q32", "quarter-units", "far-without-queue", "split-rows", "T1"])
 def test_ring_loop_with_the_list_against_the_oracle(emulators, case):
     """Three register sets: the ring loop, which issues the last slice of a block again (loaded twice, reduced once)."""
     _against_oracle(emulators["ring"], _mixed(2 + len(case)), **LOOP_CASES[case])
+
+
+@pytest.mark.parametrize("case", ["plain", "q32", "split-rows"])
+def test_ring_loop_with_the_list_on_aligner_like_input(emulators, case):
+    _against_oracle(emulators["ring"], _mixed(2 + len(case), aligner_like=True), **LOOP_CASES[case])
 
 
 def _long_blocks(seed):
@@ -260,8 +276,9 @@ def test_bit_for_bit_against_the_planes(emulators, build, lens, q32):
 
 # ---- 3. ThreadSanitizer -------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("kw", [dict(T=3, min_units=-1), dict(quarter=1, T=7, q32=1), dict(window=64, far_queue=0)],
-                         ids=["short", "quarter-q32", "far-without-queue"])
+@pytest.mark.parametrize("kw", [dict(T=3, min_units=-1), dict(quarter=1, T=7, q32=1), dict(window=64, far_queue=0),
+                                dict(T=3, min_units=-1, aligner_like=True), dict(window=64, far_queue=0, aligner_like=True)],
+                         ids=["short", "quarter-q32", "far-without-queue", "short-aligner_like", "far-without-queue-aligner_like"])
 def test_no_unordered_accesses_between_lanes(emulators, kw, monkeypatch):
     """The kernel body with the list under ThreadSanitizer (a report makes the emulator exit with 66)."""
     if emulators["tsan"] is None:
@@ -269,4 +286,5 @@ def test_no_unordered_accesses_between_lanes(emulators, kw, monkeypatch):
     monkeypatch.setenv("TSAN_OPTIONS", "halt_on_error=0 exitcode=66")
     rng = np.random.default_rng(5)
     lens = np.concatenate([np.arange(5, 257, 3), rng.integers(1, 40, 400)])
-    _against_oracle(emulators["tsan"], _lens_data(lens, 2000, 5, unique=False), **kw)
+    kw = dict(kw)
+    _against_oracle(emulators["tsan"], _lens_data(lens, 2000, 5, unique=False, aligner_like=kw.pop("aligner_like", False)), **kw)

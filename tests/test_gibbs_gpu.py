@@ -164,6 +164,52 @@ def test_exact_chain_is_the_same_for_every_team_size(n_reads, long_every, chains
     ctx.close()
 
 
+@pytest.mark.parametrize("prior", [False, True], ids=["flat", "prior"])
+def test_exact_chain_on_aligner_like_items(prior, monkeypatch):
+    """Reads that hit one transcript at several positions, items in any order (tests/aligner_like.py; Gibbs.cpp:297-311 keeps each as
+    an item of the read): a move between two items of ONE transcript leaves the counts as they were, and the team's tables see the
+    same id from one read twice.  12 000 reads = 47 tiles of 256, so a team of 17 still takes three windows, three of the reads with
+    several hundred items; the ids folded into 1..300, so that nearly every move meets the others'.  Every team size gives the same
+    integers, and they are the oracle's sequential chain's, for the first and the last chain."""
+    import aligner_like as al
+    n_reads, chains = 12_000, 3
+    M, (irp, isid, icp) = _synthetic_items(n_reads, long_row_every=4000)
+    isid = np.where(isid > 0, 1 + isid % 300, 0).astype(np.int32)
+    assert np.all(isid[irp[:-1].astype(np.int64)] == 0)                 # the noise item leads every read
+    isid = al.aligner_like(irp, isid, 77, first_fixed=True)
+    assert np.all(isid[irp[:-1].astype(np.int64)] == 0) and np.count_nonzero(isid == 0) == n_reads
+    assert int(np.diff(irp.astype(np.int64)).max()) > 512                # (three reads of 500-800 items: tiles of a few reads)
+    al.assert_on_path(al.describe(irp, isid, first_fixed=True), repeat=0.05, all_same=0.05, not_ascending=0.05)
+    init = np.zeros(M + 1, np.int32)
+    N0, pseudoC = 777, 1.0
+    alpha = np.concatenate([[1.0], np.random.default_rng(8).uniform(0.05, 3.0, M)]) if prior else None
+    eel, mw = np.full(M + 1, 700.0), np.ones(M + 1)
+    grp = np.array([1, M + 1], np.int32)
+    totc = (M + 1) * pseudoC + N0 + n_reads
+    seeds = capi().gibbs_chain_seeds(4243, chains)
+    ns = [2 + (k % 2) for k in range(chains)]
+    burnin, gap = 2, 2
+    ctx = capi().GibbsContext(M, irp, isid, icp, init, alpha, pseudoC, totc, N0, eel, mw, grp)
+    monkeypatch.setenv("RSEM_GX_TEAM", "1")
+    base, acc1, _, _ = ctx.run_chains(capi().GIBBS_EXACT, seeds, burnin, ns, gap)
+    for k in (0, chains - 1):
+        ocv, _ = orc.gibbs_chain(M, irp, isid, icp, init, alpha, pseudoC, totc, N0, eel, mw, grp, seeds[k], burnin, ns[k], gap)
+        assert np.array_equal(base[k], ocv), k
+    assert np.all(base[0].sum(1) == N0 + n_reads) and not np.array_equal(base[0][0], base[0][-1])
+    for W in (2, 7, 16, 17, 0):
+        if W:
+            monkeypatch.setenv("RSEM_GX_TEAM", str(W))
+        else:
+            monkeypatch.delenv("RSEM_GX_TEAM")  # the product's choice
+        cvs, acc, _, p = ctx.run_chains(capi().GIBBS_EXACT, seeds, burnin, ns, gap)
+        print("team", W, "->", p.team)
+        for k in range(chains):
+            assert np.array_equal(cvs[k], base[k]), (W, k)
+        for a, b in zip(acc, acc1):
+            assert np.array_equal(a, b)
+    ctx.close()
+
+
 def test_a_team_that_cannot_be_resident_gives_up_and_the_run_starts_over(monkeypatch, capfd):
     """The team barrier's way out (gibbs_exact_team.hpp: kXSpinLimit, XTeamCtl::abort).  A team needs all its workgroups on the GPU at
     once; the product guarantees that with a cooperative launch and a per-GPU lease, but another tenant's kernels can still hold the

@@ -230,6 +230,35 @@ def test_three_chains_replayed_separately(data, layout, monkeypatch):
         _same(cvs[k], ref, "chain %d (seed %d), layout %s" % (k, seeds[k], layout))
 
 
+def _aligner_like_items(d):
+    """The same reads with repeated ids and ids in any order (tests/aligner_like.py; entry 0 of every read stays)."""
+    import aligner_like as al
+    sid = al.aligner_like(d["rp"], d["sid"], 9, first_fixed=True)
+    rp = d["rp"].astype(np.int64)
+    al.assert_on_path(al.describe(rp, sid, first_fixed=True), repeat=0.05, all_same=0.05, not_ascending=0.05, same_plane=0.05, same_lane=0.05)
+    long_repeats = [i for i in np.flatnonzero(np.diff(rp) > 257) if len(np.unique(sid[rp[i] + 1:rp[i + 1]])) < rp[i + 1] - rp[i] - 1]
+    print("reads of more than 256 items with a repeated id:", [int(rp[i + 1] - rp[i]) for i in long_repeats])
+    assert long_repeats
+    return dict(d, sid=sid)
+
+
+def test_aligner_like_items_replayed_draw_for_draw(data):
+    """A read's items of ONE transcript are picks of their own with weights of their own (Gibbs.cpp:297-311): in the lane kernel two
+    lanes of a read, or one lane in two planes, add to one count; in k_sample_z_long (the reads of 300 and 700 items have repeats)
+    the chunk scans meet the id again.  One chain, every kept count vector integer for integer, as above."""
+    d = _aligner_like_items(data)
+    ctx = _ctx(d, None, 1.0)
+    order, lg, n_sell = ctx.debug_order()
+    cv, _, _ = ctx.run(capi().GIBBS_PARALLEL, 105, 0, ROUNDS, 1, 1)
+    ctx.close()
+    _check_shapes(d, order, lg, n_sell)                                  # every lane-group size, the three long reads in the CSR
+    reads = sr.Reads(d["rp"], d["sid"], d["cp"], order, lg)
+    ref, m_pick, m_gamma = sr.parallel_chain(reads, M, d["init"], None, 1.0, N0, 105, 0, ROUNDS, 1, 1)
+    _usable("aligner-like items", m_pick, m_gamma)
+    assert np.all(ref[:, d["init"] == 0].sum(1) + (ref[:, d["init"] < 0] + 1).sum(1) == N0 + d["N1"])  # every read once
+    _same(cv, ref, "aligner-like items")
+
+
 @pytest.mark.parametrize("value", ["3", "257", "0", "7x", ""])
 def test_layout_knob_rejects_what_is_not_tested(data, value, monkeypatch):
     """RSEM_GIBBS_LAYOUT_T outside 4..256, or not a number, fails the layout's construction instead of meaning the default."""

@@ -33,6 +33,17 @@ def test_group_kernel_body_equals_the_per_alignment_restatement(emulator, model_
     assert "MISMATCH" not in r.stdout
 
 
+@pytest.mark.parametrize("model_type,seed,est_rspd,has_mld", [(3, 1, 0, 0), (3, 2, 1, 0), (1, 3, 0, 0), (1, 4, 1, 1), (0, 5, 1, 0), (2, 6, 0, 0), (0, 7, 0, 1)])
+def test_group_kernel_body_on_reads_that_hit_a_transcript_twice(emulator, model_type, seed, est_rspd, has_mld):
+    """The same data with a second alignment to the same transcript on other bases, in the middle of a chunk and as the first alignment
+    of a second chunk: the run of equal windows around it is interrupted and resumes (the emulator counts such reads and fails
+    where there are none)."""
+    r = subprocess.run([emulator, str(model_type), str(seed), str(est_rspd), str(has_mld), "1"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
+    print(r.stdout[-600:])
+    assert r.returncode == 0, r.stdout[-3000:]
+    assert "MISMATCH" not in r.stdout and "interrupted and resumed" in r.stdout
+
+
 @pytest.fixture(scope="module")
 def emulator_tsan(tmp_path_factory):
     exe = os.path.join(str(tmp_path_factory.mktemp("model_emu_tsan")), "model_emu_tsan")
@@ -50,3 +61,10 @@ def test_no_unordered_accesses_between_lanes(emulator_tsan, model_type, seed, es
     global access of two lanes that no barrier orders is reported and makes the emulator exit with 66."""
     monkeypatch.setenv("TSAN_OPTIONS", "halt_on_error=0 exitcode=66")
     test_group_kernel_body_equals_the_per_alignment_restatement(emulator_tsan, model_type, seed, est_rspd, has_mld)
+
+
+@pytest.mark.skipif(not os.environ.get("RSEM_TSAN_ALL"), reason="a minute of CPU time: run with RSEM_TSAN_ALL=1")
+@pytest.mark.parametrize("model_type,seed,est_rspd,has_mld", [(3, 2, 1, 0), (0, 7, 0, 1)])
+def test_no_unordered_accesses_between_lanes_on_reads_that_hit_a_transcript_twice(emulator_tsan, model_type, seed, est_rspd, has_mld, monkeypatch):
+    monkeypatch.setenv("TSAN_OPTIONS", "halt_on_error=0 exitcode=66")
+    test_group_kernel_body_on_reads_that_hit_a_transcript_twice(emulator_tsan, model_type, seed, est_rspd, has_mld)

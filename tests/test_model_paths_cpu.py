@@ -100,3 +100,4 @@ def test_case_is_on_its_path_and_the_reference_accepts_it(name, tmp_path):
         n_row = np.diff(rp.astype(np.int64))
         keep = P["minlen"] >= mc.SEED_LEN
         assert len(n_row) == int(keep.sum()) and (n_row <= P["nal"][keep] + 1).all() and (n_row >= 1).all() and (sid <= case["M"]).all()
+        mc.assert_path_ofg(name, (M, N0, rp, sid, val))

@@ -69,6 +69,7 @@ def _reference(name, tmp_path_factory):
         for f in OUTPUTS:
             os.rename(os.path.join(d, f), os.path.join(d, "refout", os.path.basename(f)))
         r = os.path.join(d, "refout")
+        mc.assert_path_ofg(name, _read_ofg_fast(os.path.join(r, "s.ofg")))
         _REF[name] = dict(d=d, P=P, rounds=_round_lines(log), theta=rf.read_theta(os.path.join(r, "s.theta")),
                           model=rf.read_model(os.path.join(r, "s.model")), ofg=_read_ofg_fast(os.path.join(r, "s.ofg")),
                           res=rf.read_res(os.path.join(r, "s.iso_res")))

@@ -114,6 +114,35 @@ def test_parse_matches_reference_binary(name, read_type, aln, extra, tmp_path):
         assert any(f.startswith("temp/s_max") for f in _files(a))  # the filter really fired
 
 
+@pytest.mark.skipif(not os.path.exists(REF), reason="oracle/_ref/rsem-parse-alignments not built")
+def test_parse_reads_that_hit_a_transcript_twice_matches_reference_binary(tmp_path):
+    """The SAM of model_path_cases' repeat_se_q (gen_temp --near-repeat --shuffle-alignments): one read in five has two records on
+    one transcript, and a read's records come in any order.  Both parsers keep every record as a hit of its own, in file order:
+    the same files byte for byte, and s.dat is the generator's."""
+    import model_path_cases as mc
+    _need_new()
+    if not mc.have_tools(need_ref=False):
+        pytest.skip("tools/bin/gen_temp not built")
+    case = mc.CASES["repeat_se_q"]
+    d = str(tmp_path / "g")
+    mc.run([mc.GEN, d, str(case["n"]), str(case["M"]), str(case["rt"]), "7", str(case["L"]), "sam", case["iso"]] + case["opts"], 120)
+    twice = 0
+    with open(os.path.join(d, "temp", "s.dat")) as f:
+        f.readline()
+        for ln in f:
+            ids = ln.split()[1::2]
+            twice += len(set(ids)) < len(ids)
+    print("reads with two hits on one transcript:", twice)
+    assert twice >= 0.05 * case["n"]
+    a, b = str(tmp_path / "new"), str(tmp_path / "ref")
+    r1 = _run(NEW, os.path.join(d, "ref"), a, os.path.join(d, "aln.sam"), case["rt"], ("-p", "3"))
+    r2 = _run(REF, os.path.join(d, "ref"), b, os.path.join(d, "aln.sam"), case["rt"])
+    assert r2.returncode == 0, r2.stderr
+    assert r1.returncode == 0, r1.stderr
+    _same_tree(a, b)
+    assert filecmp.cmp(os.path.join(d, "temp", "s.dat"), os.path.join(a, "temp", "s.dat"), shallow=False)
+
+
 def test_parse_error_paths(tmp_path):
     """Error behaviour of SamParser.h:121-141: message on stderr, non-zero exit."""
     _need_new()

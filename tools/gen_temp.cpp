@@ -29,6 +29,12 @@
 //   --omit n               n transcripts are listed in s.omit: no read comes from them and none is aligned to them (as
 //                          rsem-parse-alignments would leave transcripts it was told to omit)
 //   --threads n            host threads (the files do not depend on it)
+//   --near-repeat n:rate   every gene sequence gets one segment of n bases copied directly behind itself, each base of the copy
+//                          substituted with probability rate (an internal repeat / tandem duplication, inside every isoform).  A
+//                          fragment that lies inside one copy gets a SECOND alignment on the other copy: same isoform, same strand,
+//                          n bases off -- in every isoform, directly behind the first.  rate 0: the two windows hold equal bases.
+//   --shuffle-alignments   (no value) each read's alignments are written in an order drawn from the read's own generator, the
+//                          same in s.dat and aln.sam -- as an aligner reports them, not ascending by transcript
 //
 // Model of the data: genes own 2..9 isoforms; every isoform is a contiguous sub-interval of its gene's
 // sequence (heavy overlap), so a read drawn from one isoform aligns, at shifted offsets, to every
@@ -52,6 +58,9 @@ struct Tx { int gene; int a, b; };  // interval of the gene sequence
 int main(int argc, char** argv) {
     // named options: everything from the first argument that starts with "--"
     int lmin = 0, lmax = 0, est_rspd = 0, frag_min = 1, frag_max = 1000, pe_cap = 400, glen_min = 1500, glen_max = 4000, n_omit = 0, n_threads = 0;
+    int rep_n = 0;
+    double rep_rate = 0.0;
+    bool shuffle_aln = false;
     double n_rate = 0.0, probF = 0.5, se_mean = -1.0, se_sd = 0.0, pe_mean = 200.0, pe_sd = 30.0;
     bool opt_probF = false;
     {
@@ -59,6 +68,7 @@ int main(int argc, char** argv) {
         for (int i = 1; i < argc; i++) if (argv[i][0] == '-' && argv[i][1] == '-') { first_opt = i; break; }
         for (int i = first_opt; i < argc; i += 2) {
             const std::string o = argv[i];
+            if (o == "--shuffle-alignments") { shuffle_aln = true; --i; continue; }  // (a flag: no value follows)
             const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
             bool ok = v != nullptr;
             if (!ok) {}
@@ -71,6 +81,7 @@ int main(int argc, char** argv) {
             else if (o == "--pe-frag") ok = sscanf(v, "%lf,%lf,%d", &pe_mean, &pe_sd, &pe_cap) == 3 && pe_sd >= 0.0 && pe_cap >= 1;
             else if (o == "--gene-len") ok = sscanf(v, "%d-%d", &glen_min, &glen_max) == 2 && glen_min >= 700 && glen_max >= glen_min;
             else if (o == "--omit") ok = sscanf(v, "%d", &n_omit) == 1 && n_omit >= 0;
+            else if (o == "--near-repeat") ok = sscanf(v, "%d:%lf", &rep_n, &rep_rate) == 2 && rep_n >= 1 && rep_rate >= 0.0 && rep_rate <= 1.0;
             else if (o == "--threads") ok = sscanf(v, "%d", &n_threads) == 1 && n_threads >= 1;
             else ok = false;
             if (!ok) { fprintf(stderr, "gen_temp: bad option %s %s\n", o.c_str(), v ? v : ""); return 1; }
@@ -94,6 +105,7 @@ int main(int argc, char** argv) {
     const bool var_len = lmin < lmax;
     const int Lbuf = std::max(L, lmax);
     if (n_omit >= M) { fprintf(stderr, "--omit: fewer than M\n"); return 1; }
+    if (rep_n > glen_min - 600) { fprintf(stderr, "--near-repeat: the segment must lie inside every isoform (n <= gene length - 600)\n"); return 1; }
     if (glen_min - 600 < Lbuf) { fprintf(stderr, "--gene-len: an isoform (gene length - 600) must hold a read\n"); return 1; }
     if (lmax > frag_max || (pe && std::min(pe_cap, frag_max) < lmax)) { fprintf(stderr, "--frag-range / --pe-frag: a fragment must hold a read\n"); return 1; }
     std::mt19937_64 rng(seed);
@@ -115,6 +127,25 @@ int main(int argc, char** argv) {
     }
     gstart.push_back(M + 1);
     const int m = (int)gseq.size();
+    // --near-repeat: gene coordinates [rep_at[g], + n) and [rep_at[g] + n, + n) hold the two copies; drawn by a generator of their own
+    std::vector<int> rep_at(m, 0);
+    if (rep_n > 0) {
+        std::mt19937_64 rr(((uint64_t)seed << 1) ^ 0x72657065ull);
+        for (int g = 0; g < m; g++) {
+            std::string& s = gseq[g];
+            const int Lg = (int)s.size();
+            rep_at[g] = 300 + (int)(rr() % (uint64_t)(Lg - 600 - rep_n + 1));  // inside [300, Lg - 300): part of every isoform
+            std::string copy = s.substr((size_t)rep_at[g], (size_t)rep_n);
+            for (char& c : copy)
+                if ((double)(rr() >> 11) * (1.0 / 9007199254740992.0) < rep_rate) {
+                    int b = 0;
+                    while (BASES[b] != c) ++b;
+                    c = BASES[(b + 1 + (int)(rr() % 3)) & 3];  // another base
+                }
+            s.insert((size_t)(rep_at[g] + rep_n), copy);
+        }
+        for (int t = 1; t <= M; t++) tx[t].b += rep_n;  // (every isoform ends behind the second copy)
+    }
     auto tlen = [&](int t) { return tx[t].b - tx[t].a; };
 
     std::string cmd = "mkdir -p " + out + "/temp " + out + "/stat";
@@ -222,6 +253,7 @@ int main(int argc, char** argv) {
         O.q1.reserve((size_t)(r1 - r0) * (2 * Lbuf + 20));
         if (pe) O.q2.reserve((size_t)(r1 - r0) * (2 * Lbuf + 20));
         std::string line;
+        std::vector<std::pair<int, int>> alns;  // (transcript, forward coordinate of the fragment in it)
         for (long long r = r0; r < r1; r++) {
             double u = tuni(0, cdf[M]);
             int t = (int)(std::upper_bound(cdf.begin(), cdf.end(), u) - cdf.begin());
@@ -252,25 +284,36 @@ int main(int argc, char** argv) {
             if (pe) emit_read(O.q2, r, seq2, qual2);
             // alignments: every isoform of the gene that contains [gpos, gpos+frag)
             line.clear();
-            int k = 0;
             const int g = tx[t].gene;
+            alns.clear();
+            int other = -1;  // --near-repeat: the fragment's place on the other copy, where it lies inside one
+            if (rep_n > 0 && frag <= rep_n) {
+                if (gpos >= rep_at[g] && gpos + frag <= rep_at[g] + rep_n) other = gpos + rep_n;
+                else if (gpos >= rep_at[g] + rep_n && gpos + frag <= rep_at[g] + 2 * rep_n) other = gpos - rep_n;
+            }
             for (int sv = gstart[g]; sv < gstart[g + 1]; sv++) {
                 if (tx[sv].a <= gpos && gpos + frag <= tx[sv].b && !omitted[sv]) {
-                    const int sl = tlen(sv), f2 = gpos - tx[sv].a;
-                    const int p = dir == 0 ? f2 : sl - f2 - frag;
-                    if (pe) snprintf(tmp, sizeof(tmp), " %d %d %d", dir == 0 ? sv : -sv, p, frag);
-                    else snprintf(tmp, sizeof(tmp), " %d %d", dir == 0 ? sv : -sv, p);
-                    line += tmp;
-                    ++k;
-                    if (want_sam) {
-                        if (!pe) sam_rec(r, dir == 0 ? 0 : 16, sv, f2, 0, 0, seq, qual, dir != 0);
-                        else if (dir == 0) {
-                            sam_rec(r, 99, sv, f2, f2 + frag - len2, frag, seq, qual, false);
-                            sam_rec(r, 147, sv, f2 + frag - len2, f2, -frag, seq2, qual2, true);
-                        } else {
-                            sam_rec(r, 83, sv, f2 + frag - len1, f2, -frag, seq, qual, true);
-                            sam_rec(r, 163, sv, f2, f2 + frag - len1, frag, seq2, qual2, false);
-                        }
+                    alns.push_back({sv, gpos - tx[sv].a});
+                    if (other >= 0 && tx[sv].a <= other && other + frag <= tx[sv].b) alns.push_back({sv, other - tx[sv].a});
+                }
+            }
+            if (shuffle_aln)
+                for (size_t i = alns.size(); i > 1; i--) std::swap(alns[i - 1], alns[(size_t)(rg() % (uint64_t)i)]);
+            const int k = (int)alns.size();
+            for (const auto& al : alns) {
+                const int sv = al.first, f2 = al.second, sl = tlen(sv);
+                const int p = dir == 0 ? f2 : sl - f2 - frag;
+                if (pe) snprintf(tmp, sizeof(tmp), " %d %d %d", dir == 0 ? sv : -sv, p, frag);
+                else snprintf(tmp, sizeof(tmp), " %d %d", dir == 0 ? sv : -sv, p);
+                line += tmp;
+                if (want_sam) {
+                    if (!pe) sam_rec(r, dir == 0 ? 0 : 16, sv, f2, 0, 0, seq, qual, dir != 0);
+                    else if (dir == 0) {
+                        sam_rec(r, 99, sv, f2, f2 + frag - len2, frag, seq, qual, false);
+                        sam_rec(r, 147, sv, f2 + frag - len2, f2, -frag, seq2, qual2, true);
+                    } else {
+                        sam_rec(r, 83, sv, f2 + frag - len1, f2, -frag, seq, qual, true);
+                        sam_rec(r, 163, sv, f2, f2 + frag - len1, frag, seq2, qual2, false);
                     }
                 }
             }
