@@ -475,6 +475,58 @@ typedef struct rsem_depth_info {
 int rsem_depth_accumulate(int device, uint64_t n_bases, uint64_t n_blocks, const uint64_t* start, const uint32_t* len, const double* w,
                           double* depth /* n_bases, in and out */, rsem_depth_info* info /* may be NULL */);
 
+/* ---- transcript coordinates -> genome coordinates, and the per-read collapse (rsem-tbam2gbam) -----------------
+ * rsem_gmap_create keeps the reference of BamConverter (BamConverter.h:45-73, Transcripts of a type-0 .ti): per transcript its
+ * strand ('+' or '-'), its length without poly-A tail, the tid of its chromosome in the output header, and its exons
+ * exon_off[t] .. exon_off[t + 1] - 1 of the flat arrays (1-based, inclusive, ascending).  Refused (RSEM_ERR_INVALID): a negative
+ * count or tid, another strand, a transcript without exons or with more than 32766 (n_cigar is 16 bits in BAM), exons that are
+ * empty, overlap or descend, exons whose bases do not add up to `length` (tr2chr walks the exons AND uses the length: sam_utils.h:
+ * 138-181).  Nothing is uploaded before the first rsem_gmap_convert that has an alignment: creating needs no device.
+ *
+ * rsem_gmap_convert takes whole groups -- group g is the alignments group_off[g] .. group_off[g + 1] - 1, the consecutive records of
+ * one read -- of single-end (mates = 1) or paired-end (mates = 2) alignments; the mates of alignment a are a * mates and
+ * a * mates + 1 of the per-mate arrays, read 1 first.  No names, sequences or tags are passed.
+ *   per mate, replacing convert + tr2chr (BamConverter.h:150-191, sam_utils.h:137-208) and bam_endpos / hts_reg2bin of htslib 1.3
+ *   (sam.c:327-342): the range pos + 1 .. pos + l_qseq of transcript tr (the record's own CIGAR is ignored), mirrored on a '-'
+ *   transcript, becomes out_tid, out_pos (0-based), out_n_cigar alternating M / N words with I for the bases off either end of the
+ *   transcript (one I for a read wholly in the poly-A tail), out_bin, out_has_n (the CIGAR has an N: XS:A is due); out_flag is flag
+ *   with 0x10 flipped on '-', and 0x20 too where 0x1 is set.  The words of mate i are cigar_words[cigar_off[i] .. cigar_off[i + 1]);
+ *   cigar_off has one element more than there are mates.  cigar_cap is the room in cigar_words: the sum over the mates of
+ *   2 * (exons of the transcript) + 2 always suffices; less than what is needed is RSEM_ERR_INVALID.
+ *   per group, replacing CollapseMap (bc_aux.h:9-118) and the order of writeCollapsedLines (BamConverter.h:193-218): alignments
+ *   whose converted (tid, pos, reverse bit, n_cigar, CIGAR words) of mate 1, then of mate 2, are equal become one, the first in
+ *   file order; its weight is the float fold w_first + w_next + ... in file order; the group comes out in the order of that key.
+ *   out_src[k] is the alignment (index in the call) that is written k-th and out_w[k] its folded weight; both have room for
+ *   n_alignments, info->n_alignments_out say how many count; the groups come out in their order.
+ * MAPQ is not computed here: it is glibc's log10 of the folded float on the host (sam_utils.h:72-76).
+ * Checked before a device is touched (RSEM_ERR_INVALID): a NULL handle, mates other than 1 or 2, negative counts, group_off that
+ * does not start at 0, end at n_alignments and strictly ascend, a transcript index outside the reference, pos < 0, l_qseq < 1.
+ * The groups go through in batches: whole groups in order while their alignments stay within the budget of 2^22, a group above the
+ * budget a batch of its own.  The environment variable RSEM_GMAP_BATCH_ITEMS (a whole number >= 1; anything else:
+ * RSEM_ERR_INVALID), read at every call, replaces the budget (a test knob: the results do not depend on it, n_batches does).
+ * The handle's device buffers grow to the largest batch seen and are kept; calls on one handle are serialised. */
+typedef struct rsem_gmap rsem_gmap;
+typedef struct rsem_gmap_info {
+    uint64_t n_groups;
+    uint64_t n_alignments_in;
+    uint64_t n_alignments_out;
+    uint64_t n_cigar_words;
+    int32_t n_batches;
+    int32_t n_launches;        /* kernels and library scans: six per batch */
+    uint64_t batch_items;      /* the budget in force */
+    uint64_t device_bytes;     /* held by the handle after the call */
+    double upload_ms;          /* the batches' fields to the device */
+    double kernel_ms;          /* the batches' kernels and scans */
+} rsem_gmap_info;
+int rsem_gmap_create(rsem_gmap** out, int device, int32_t n_transcripts, const uint8_t* strand, const int32_t* length, const int32_t* out_tid,
+                     const uint64_t* exon_off /* n_transcripts + 1 */, const int32_t* exon_start, const int32_t* exon_end);
+int rsem_gmap_convert(rsem_gmap* h, int32_t mates, int64_t n_alignments, int64_t n_groups, const uint64_t* group_off /* n_groups + 1 */,
+                      const int32_t* tr, const int32_t* pos, const int32_t* l_qseq, const uint32_t* flag /* per mate */,
+                      const float* w /* per alignment */, int32_t* out_tid, int32_t* out_pos, uint32_t* out_flag, uint32_t* out_n_cigar,
+                      uint32_t* out_bin, uint32_t* out_has_n /* per mate */, uint64_t* cigar_off /* mates + 1 */, uint32_t* cigar_words,
+                      uint64_t cigar_cap, uint64_t* out_src, float* out_w /* n_alignments */, rsem_gmap_info* info /* may be NULL */);
+void rsem_gmap_destroy(rsem_gmap* h);
+
 #ifdef __cplusplus
 }
 #endif

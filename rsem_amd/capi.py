@@ -55,6 +55,12 @@ class DepthInfo(C.Structure):
                 ("batch_items", C.c_uint64), ("device_bytes", C.c_uint64), ("upload_ms", C.c_double), ("kernel_ms", C.c_double)]
 
 
+class GmapInfo(C.Structure):
+    _fields_ = [("n_groups", C.c_uint64), ("n_alignments_in", C.c_uint64), ("n_alignments_out", C.c_uint64), ("n_cigar_words", C.c_uint64),
+                ("n_batches", C.c_int32), ("n_launches", C.c_int32), ("batch_items", C.c_uint64), ("device_bytes", C.c_uint64),
+                ("upload_ms", C.c_double), ("kernel_ms", C.c_double)]
+
+
 class EmProfile(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("estep_ms_sum", C.c_double), ("estep_launches", C.c_int32),
                 ("rounds", C.c_int32), ("algorithmic_bytes_per_round", C.c_uint64)]
@@ -123,6 +129,10 @@ def lib():
         L.rsem_ci_intervals.argtypes = [ci, C.c_int64, i32, _f32p, dbl, _f32p, _f32p, _f32p]
         L.rsem_kmer_shared_counts.argtypes = [ci, i32, _u64p, vp, i32, _u32p, vp]
         L.rsem_depth_accumulate.argtypes = [ci, u64, u64, vp, vp, vp, vp, vp]
+        L.rsem_gmap_create.argtypes = [C.POINTER(vp), ci, i32, vp, vp, vp, vp, vp, vp]
+        L.rsem_gmap_convert.argtypes = [vp, i32, C.c_int64, C.c_int64] + [vp] * 14 + [u64, vp, vp, vp]
+        L.rsem_gmap_destroy.argtypes = [vp]
+        L.rsem_gmap_destroy.restype = None
         _lib = L
     return _lib
 
@@ -496,3 +506,63 @@ def ci_calculate_samples(tpm_samples, l_bars, gene_starts, confidence=0.95, tran
                                            _ptr(out.get("iso_fpkm")), C.addressof(prof)))
     out["profile"] = prof
     return out
+
+
+class Gmap:
+    """rsem_gmap: transcript coordinates -> genome coordinates and the per-read collapse of rsem-tbam2gbam.  strand: '+' / '-' per
+    transcript (a str, bytes or uint8 array); exon_off: n + 1 offsets into exon_start / exon_end (1-based, inclusive)."""
+
+    def __init__(self, strand, length, out_tid, exon_off, exon_start, exon_end, device=0):
+        if isinstance(strand, str):
+            strand = strand.encode()
+        self.strand = np.frombuffer(strand, np.uint8).copy() if isinstance(strand, (bytes, bytearray)) else np.ascontiguousarray(strand, np.uint8)
+        self.length = np.ascontiguousarray(length, np.int32)
+        self.out_tid = np.ascontiguousarray(out_tid, np.int32)
+        self.exon_off = np.ascontiguousarray(exon_off, np.uint64)
+        self.exon_start = np.ascontiguousarray(exon_start, np.int32)
+        self.exon_end = np.ascontiguousarray(exon_end, np.int32)
+        n = len(self.length)
+        assert len(self.strand) == n and len(self.out_tid) == n and len(self.exon_off) == n + 1
+        assert len(self.exon_start) == len(self.exon_end) and (n == 0 or len(self.exon_start) >= int(self.exon_off[-1]))
+        self.h = C.c_void_p()
+        _check(lib().rsem_gmap_create(C.byref(self.h), device, n, _ptr(self.strand), _ptr(self.length), _ptr(self.out_tid), _ptr(self.exon_off),
+                                      _ptr(self.exon_start), _ptr(self.exon_end)))
+
+    def convert(self, mates, group_off, tr, pos, l_qseq, flag, w):
+        """rsem_gmap_convert.  Returns a dict: per mate tid, pos, flag, n_cigar, bin, has_n; cigar_off (mates + 1) and cigar (the words);
+        out_src, out_w (the kept alignments in output order, their folded weights); info."""
+        group_off = np.ascontiguousarray(group_off, np.uint64)
+        tr, pos, l_qseq = (np.ascontiguousarray(x, np.int32) for x in (tr, pos, l_qseq))
+        flag = np.ascontiguousarray(flag, np.uint32)
+        w = np.ascontiguousarray(w, np.float32)
+        n_aln, n_mates = len(w), len(tr)
+        assert n_mates == n_aln * mates or mates not in (1, 2)
+        assert len(pos) == n_mates and len(l_qseq) == n_mates and len(flag) == n_mates and len(group_off) >= 1
+        ok = (tr >= 0) & (tr < len(self.length))
+        exons = (self.exon_off[1:] - self.exon_off[:-1]).astype(np.int64)
+        cap = int(np.sum(2 * exons[tr[ok]] + 2)) if n_mates else 0  # the bound include/rsem_hip.h states
+        o = {k: np.zeros(n_mates, t) for k, t in (("tid", np.int32), ("pos", np.int32), ("flag", np.uint32), ("n_cigar", np.uint32),
+                                                  ("bin", np.uint32), ("has_n", np.uint32))}
+        cigar_off = np.zeros(n_mates + 1, np.uint64)
+        cigar = np.zeros(max(cap, 1), np.uint32)
+        out_src, out_w = np.zeros(max(n_aln, 1), np.uint64), np.zeros(max(n_aln, 1), np.float32)
+        info = GmapInfo()
+        _check(lib().rsem_gmap_convert(self.h, mates, n_aln, len(group_off) - 1, _ptr(group_off), _ptr(tr), _ptr(pos), _ptr(l_qseq), _ptr(flag), _ptr(w),
+                                       _ptr(o["tid"]), _ptr(o["pos"]), _ptr(o["flag"]), _ptr(o["n_cigar"]), _ptr(o["bin"]), _ptr(o["has_n"]),
+                                       _ptr(cigar_off), _ptr(cigar), cap, _ptr(out_src), _ptr(out_w), C.addressof(info)))
+        o["cigar_off"] = cigar_off
+        o["cigar"] = cigar[:int(cigar_off[-1])]
+        o["out_src"], o["out_w"] = out_src[:info.n_alignments_out], out_w[:info.n_alignments_out]
+        o["info"] = {f: getattr(info, f) for f, _ in GmapInfo._fields_}
+        return o
+
+    def close(self):
+        if self.h:
+            lib().rsem_gmap_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

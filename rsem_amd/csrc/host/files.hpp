@@ -273,6 +273,8 @@ inline RefInfo load_refs(const std::string& path, bool with_seq) {
 struct TranscriptInfo {  // ref.ti (Transcripts.h:81-94, Transcript.h:119-148)
     std::string transcript_id, transcript_name, gene_id, gene_name, seqname;
     int length = 0;
+    char strand = '+';                              // rsem-tbam2gbam reads these two
+    std::vector<std::pair<int, int>> structure;     // exons: start, end (1-based, inclusive)
 };
 
 struct Transcripts {
@@ -310,7 +312,16 @@ inline Transcripts load_transcripts(const std::string& path) {
         getl(s);  // strand length
         char strand;
         if (sscanf(s.c_str(), " %c %d", &strand, &x.length) != 2) die("%s: bad transcript record %d", path.c_str(), i);
+        x.strand = strand;
         getl(s);  // structure
+        {
+            char* q = nullptr;
+            const long n_ex = strtol(s.c_str(), &q, 10);
+            for (long k = 0; k < n_ex; k++) {
+                const long a = strtol(q, &q, 10), b = strtol(q, &q, 10);
+                x.structure.push_back({(int)a, (int)b});
+            }
+        }
         getl(s);  // left
     }
     free(line);
