@@ -348,6 +348,10 @@ int rsem_gibbs_debug_order(rsem_gibbs_ctx* ctx, uint32_t* order, uint8_t* lg, ui
  * The environment variable RSEM_GIBBS_LAYOUT_T (a whole number in 4..256; anything else makes building the layout fail with
  * RSEM_ERR_INVALID), read when the layout is built, sets T (a measurement / test knob). */
 int rsem_gibbs_debug_units(rsem_gibbs_ctx* ctx, uint32_t* T, uint32_t* n_units_io, uint32_t* out);
+/* ... and the LDS window of every unit, in the same order (reads only): 2 words per unit, the first id of the window and the ids
+ * it holds.  An anchor id above 2^23 - 1 is kept as 2^23 - 1 (sell_layout.hpp kKeyMinSidCap): a unit of such reads alone has its
+ * window there, one id wide where none of its ids comes that far down, and takes the far path. */
+int rsem_gibbs_debug_unit_windows(rsem_gibbs_ctx* ctx, uint32_t* n_units_io, int32_t* out);
 int rsem_gibbs_destroy(rsem_gibbs_ctx* ctx);
 /* sampling.h:19-44: seeds of the first nchains chains for --seed seed. */
 int rsem_gibbs_chain_seeds(uint32_t seed, int nchains, uint32_t* out);

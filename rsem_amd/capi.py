@@ -111,6 +111,7 @@ def lib():
         L.rsem_gibbs_get_pve_c_trans.argtypes = [vp, _f64p]
         L.rsem_gibbs_debug_order.argtypes = [vp, _u32p, _u8p, C.POINTER(C.c_uint32)]
         L.rsem_gibbs_debug_units.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp]
+        L.rsem_gibbs_debug_unit_windows.argtypes = [vp, C.POINTER(C.c_uint32), vp]
         L.rsem_gibbs_destroy.argtypes = [vp]
         L.rsem_comm_unique_id.argtypes = [C.c_char_p]
         L.rsem_comm_create.argtypes = [C.POINTER(vp), ci, ci, ci, C.c_char_p]
@@ -305,6 +306,14 @@ class GibbsContext:
         out = np.zeros((n.value, 6), np.uint32)
         _check(lib().rsem_gibbs_debug_units(self._h, C.byref(T), C.byref(n), out.ctypes.data))
         return int(T.value), out
+
+    def debug_unit_windows(self):
+        """rsem_gibbs_debug_unit_windows: windows[u] = (first id, ids) of the LDS window of unit u of debug_units()."""
+        n = C.c_uint32(0)
+        _check(lib().rsem_gibbs_debug_unit_windows(self._h, C.byref(n), None))
+        out = np.zeros((n.value, 2), np.int32)
+        _check(lib().rsem_gibbs_debug_unit_windows(self._h, C.byref(n), out.ctypes.data))
+        return out
 
     def set_allele_groups(self, ta):
         ta = np.ascontiguousarray(ta, np.int32)

@@ -635,6 +635,22 @@ int rsem_gibbs_debug_units(rsem_gibbs_ctx* c, uint32_t* T, uint32_t* n_units_io,
     return RSEM_OK;
 }
 
+int rsem_gibbs_debug_unit_windows(rsem_gibbs_ctx* c, uint32_t* n_units_io, int32_t* out) {
+    RSEM_REQUIRE(c && n_units_io, "NULL argument");
+    RSEM_HIP_TRY(hipSetDevice(c->device));
+    int rc = ensure_parallel_layout(c);
+    if (rc != RSEM_OK) return rc;
+    const uint32_t cap = *n_units_io;
+    *n_units_io = (uint32_t)c->h_units.size();
+    if (!out) return RSEM_OK;
+    RSEM_REQUIRE(cap >= c->h_units.size(), "out holds fewer units than the layout has");
+    for (size_t u = 0; u < c->h_units.size(); u++) {
+        out[2 * u] = c->h_units[u].base;
+        out[2 * u + 1] = c->h_units[u].span;
+    }
+    return RSEM_OK;
+}
+
 int rsem_gibbs_create(rsem_gibbs_ctx** out, int device, int32_t M, uint64_t N1, uint64_t nitems, const uint64_t* row_ptr,
                       const int32_t* sid, const double* conprb, const int32_t* init_counts, const double* alpha,
                       double pseudoC, double totc, uint64_t N0, const double* eel, const double* mw, int32_t m,

@@ -8,6 +8,7 @@
 //   depth_check wig <alignments> <out> <track name> [--no-fractional-weight]
 //   depth_check readdepth <alignments> <out>
 //   depth_check fold <n_bases> < "start len weight-bits-as-hex" lines      prints the depth's bits, one base a line
+//   depth_check tilebits <n_tiles> ...                                     prints tile_bits of every number
 // Build: hipcc (host compilation of the HIP headers simt_emu.hpp pulls in) -DRSEM_EMU -fsanitize=address,undefined -fno-gpu-sanitize
 #include "simt_emu.hpp"
 
@@ -56,6 +57,8 @@ extern "C" int rsem_depth_accumulate(int, uint64_t n_bases, uint64_t n_blocks, c
     if (info) { memset(info, 0, sizeof(*info)); info->batch_items = budget; }
     if (!n_blocks || !n_bases) return RSEM_OK;
     Job* J = new Job();
+    const int bits = tile_bits((n_bases + kTile - 1) / kTile);  // depth.hip: the radix sort's end_bit
+    const uint32_t key_mask = bits >= 32 ? 0xffffffffu : (1u << bits) - 1u;
     pthread_barrier_init(&J->blk.bar, nullptr, 256);
     for (int k = 0; k < 4; k++) pthread_barrier_init(&J->blk.w[k].bar, nullptr, 64);
     for (uint64_t lo = 0; lo < n_blocks;) {
@@ -66,12 +69,15 @@ extern "C" int rsem_depth_accumulate(int, uint64_t n_bases, uint64_t n_blocks, c
         for (uint64_t b = lo; b < hi; b++)
             for (uint64_t t = 0; t < tiles_of(start[b], len[b]); t++) ent.push_back({(uint32_t)(first_tile(start[b]) + t), (uint32_t)(b - lo)});
         if (ent.size() != entries) { g_error = "batch_end counts other entries than tiles_of"; return RSEM_ERR_STATE; }
-        std::stable_sort(ent.begin(), ent.end(), [](const auto& a, const auto& b) { return a.first < b.first; });  // on the tile ALONE
+        // on the tile ALONE, and like the radix sort on no more of its bits than tile_bits names
+        std::stable_sort(ent.begin(), ent.end(), [key_mask](const auto& a, const auto& b) { return (a.first & key_mask) < (b.first & key_mask); });
         std::vector<uint32_t> blk_of(ent.size());
         for (size_t i = 0; i < ent.size(); i++) blk_of[i] = ent[i].second;
         for (size_t i = 0; i < ent.size();) {  // the run-length encoding of the tiles; one workgroup each
             size_t j = i;
             while (j < ent.size() && ent[j].first == ent[i].first) j++;
+            // a tile is ONE run, one workgroup: two of a launch would both write its bases
+            if (i > 0 && ent[i].first <= ent[i - 1].first) { g_error = "the sorted tiles do not ascend"; return RSEM_ERR_STATE; }
             J->tile = ent[i].first; J->e0 = (uint32_t)i; J->ne = (uint32_t)(j - i);
             J->blk_of = blk_of.data(); J->start = start + lo; J->len = len + lo; J->w = w + lo; J->depth = depth; J->n_bases = n_bases;
             std::vector<std::thread> th;
@@ -110,6 +116,10 @@ int main(int argc, char* argv[]) {
             printf("%016llx\n", bits);
         }
         fprintf(stderr, "batches %d entries %llu tiles %llu\n", info.n_batches, (unsigned long long)info.n_entries, (unsigned long long)info.n_tiles_touched);
+        return 0;
+    }
+    if (argc >= 3 && !strcmp(argv[1], "tilebits")) {
+        for (int i = 2; i < argc; i++) printf("%d\n", tile_bits(strtoull(argv[i], nullptr, 10)));
         return 0;
     }
     DepthOptions opt;

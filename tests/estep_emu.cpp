@@ -185,7 +185,10 @@ int main(int argc, char** argv) {
         if (fv < kEpsilon) fv = 0.0;
         counts[e.sid] += fv * xinv[e.slot - H.x_slot_base];
     }
-    fprintf(stderr, "estep_emu: %zu far entries of split rows\n", H.far.size());
+    uint32_t n_split = 0;
+    for (const Shape& S : H.shapes) n_split += S.fmt == kFmtF64X ? S.n_rows : 0u;
+    fprintf(stderr, "estep_emu: %zu far entries of split rows, %u split rows, %llu apart rows, anchor sum %llu\n", H.far.size(), n_split,
+            (unsigned long long)H.n_apart_rows, (unsigned long long)H.anchor_sum);
     f = fopen(argv[2], "wb");
     if (!f) return 4;
     fwrite(counts.data(), 8, counts.size(), f);

@@ -8,6 +8,8 @@
 //
 //   gmap_check convert <reference_name> <alignments> <out.bam> [-p N]     the recorded CL: is that of "rsem-tbam2gbam <the three names>"
 //   gmap_check collapse <n> <run>      a group of n alignments in runs of `run` equal keys against std::map, both widths' seams
+//   gmap_check fields < text           transcripts and a case (tests/gmap_limits.py: fields_input) -> every mate's fields and words, the kept
+//                                      alignments and their weights' bits, the batches
 // Build: hipcc (host compilation of the HIP headers simt_emu.hpp pulls in) -DRSEM_EMU -fsanitize=address,undefined -fno-gpu-sanitize
 #include "simt_emu.hpp"
 
@@ -189,6 +191,65 @@ int main(int argc, char* argv[]) {
         printf("ok %zu\n", want.size());
         return 0;
     }
-    fprintf(stderr, "usage: gmap_check convert|collapse ...\n");
+    if (argc == 2 && !strcmp(argv[1], "fields")) {
+        unsigned long long n_tr, n_ex, x, y, z, v;
+        if (scanf("%llu %llu", &n_tr, &n_ex) != 2) return 2;
+        std::vector<uint8_t> strand(n_tr);
+        std::vector<int32_t> length(n_tr), tid(n_tr), st(n_ex), en(n_ex);
+        std::vector<uint64_t> eoff(n_tr + 1, 0);
+        for (size_t t = 0; t < n_tr; t++) {
+            if (scanf("%llu %llu %llu %llu", &x, &y, &z, &v) != 4) return 2;
+            strand[t] = (uint8_t)x; length[t] = (int32_t)y; tid[t] = (int32_t)z; eoff[t + 1] = v;
+        }
+        for (size_t e = 0; e < n_ex; e++) {
+            if (scanf("%llu %llu", &x, &y) != 2) return 2;
+            st[e] = (int32_t)x; en[e] = (int32_t)y;
+        }
+        unsigned long long mates, n, ng;
+        if (scanf("%llu %llu %llu", &mates, &n, &ng) != 3) return 2;
+        const size_t nm = n * mates;
+        std::vector<uint64_t> goff(ng + 1), coff(nm + 1), osrc(n);
+        for (auto& g : goff) { if (scanf("%llu", &x) != 1) return 2; g = x; }
+        std::vector<int32_t> tr(nm), pos(nm), lq(nm), otid(nm), opos(nm);
+        std::vector<uint32_t> flag(nm), of(nm), onc(nm), ob(nm), ohn(nm);
+        std::vector<float> w(n), ow(n);
+        size_t cap = 0;
+        for (size_t i = 0; i < nm; i++) {
+            if (scanf("%llu %llu %llu %llu", &x, &y, &z, &v) != 4 || x >= n_tr) return 2;
+            tr[i] = (int32_t)x; pos[i] = (int32_t)y; lq[i] = (int32_t)z; flag[i] = (uint32_t)v;
+            cap += 2 * (eoff[x + 1] - eoff[x]) + 2;  // the bound include/rsem_hip.h states
+        }
+        for (size_t a = 0; a < n; a++) {
+            unsigned b;
+            if (scanf("%x", &b) != 1) return 2;
+            memcpy(&w[a], &b, 4);
+        }
+        std::vector<uint32_t> cig(cap);
+        rsem_gmap* h = nullptr;
+        if (rsem_gmap_create(&h, 0, (int32_t)n_tr, strand.data(), length.data(), tid.data(), eoff.data(), st.data(), en.data()) != RSEM_OK) {
+            fprintf(stderr, "%s\n", g_error.c_str());
+            return 2;
+        }
+        rsem_gmap_info info;
+        if (rsem_gmap_convert(h, (int32_t)mates, (int64_t)n, (int64_t)ng, goff.data(), tr.data(), pos.data(), lq.data(), flag.data(), w.data(), otid.data(), opos.data(),
+                              of.data(), onc.data(), ob.data(), ohn.data(), coff.data(), cig.data(), cig.size(), osrc.data(), ow.data(), &info) != RSEM_OK) {
+            fprintf(stderr, "%s\n", g_error.c_str());
+            return 2;
+        }
+        rsem_gmap_destroy(h);
+        for (size_t i = 0; i < nm; i++) {
+            printf("%d %d %u %u %u %u", otid[i], opos[i], of[i], onc[i], ob[i], ohn[i]);
+            for (uint64_t k = coff[i]; k < coff[i + 1]; k++) printf(" %u", cig[k]);
+            printf("\n");
+        }
+        for (uint64_t k = 0; k < info.n_alignments_out; k++) {
+            unsigned b;
+            memcpy(&b, &ow[k], 4);
+            printf("out %llu %08x\n", (unsigned long long)osrc[k], b);
+        }
+        fprintf(stderr, "batches %d\n", info.n_batches);
+        return 0;
+    }
+    fprintf(stderr, "usage: gmap_check convert|collapse|fields ...\n");
     return 2;
 }

@@ -255,7 +255,7 @@ def tr2chr(t, sp, ep):
         i += 1
         if i >= len(ex):
             break
-        words.append((ex[i][0] - ex[i - 1][1] - 1) << 4 | 3)
+        words.append(((ex[i][0] - ex[i - 1][1] - 1) << 4 | 3) & 0xffffffff)  # a CIGAR word has 32 bits: an intron of 2^28 bases or more wraps
         sp = cur + 1
         cur += ex[i][1] - ex[i][0] + 1
     words.append((ep - L) << 4 | 1 if i >= len(ex) else (ep - sp + 1) << 4 | 0)

@@ -6,7 +6,11 @@
 //                            separator search and the rolled keys (lane_starts, the body k_tile runs), one stable sort per
 //                            chunk (last chunk first) over key_bits bits, head flags, group indices, shared flags from neighbours, per-wave runs -- over random
 //                            two- and five-letter sequences at k = 1, 2, 25, 26, 27, 28, 54, 55, 60, whole and in batches, and
-//                            compares every step with brute force.  Prints "ok <cases>".
+//                            compares every step with brute force; then the constructions of tests/kmer_limits.py: sequences of
+//                            k + 40 bases that differ in one base of the first, the last, a middle chunk or in base 27, at k = 81,
+//                            82, 108, 109 and 2049, and separators on the word, lane and tile seams of the separated layout with
+//                            runs of empty transcripts, at k = 1, 8, 25, 28.  Prints "ok <cases>".
+//   kmer_check limits        those constructions alone.
 //   kmer_check fasta FILE    prints the reader's entries as name <TAB> bases (after its warnings).
 #include <algorithm>
 #include <cstdio>
@@ -57,6 +61,48 @@ Input random_input(std::mt19937& rng, int letters, int M, int max_len) {
             in.seq_off.push_back(in.codes.size());
         }
     }
+    return in;
+}
+
+void add_seq(Input& in, const std::vector<uint8_t>& s) {
+    in.codes.insert(in.codes.end(), s.begin(), s.end());
+    in.seq_off.push_back(in.codes.size());
+}
+
+// tests/kmer_limits.py: large_k_seqs
+Input large_k_input(std::mt19937& rng, int k) {
+    std::vector<uint8_t> a(k + 40);
+    for (auto& c : a) c = (uint8_t)(rng() % 4);
+    const int nc = n_chunks(k), mid = kChunkBases * (nc / 2);
+    Input in;
+    add_seq(in, a);
+    for (int at : {0, k + 39, mid, kChunkBases, kChunkBases - 1, kChunkBases * (nc - 1), kChunkBases * (nc - 1) - 1}) {
+        std::vector<uint8_t> s = a;
+        s[at] = (uint8_t)((s[at] + 1) % 4);
+        add_seq(in, s);
+    }
+    add_seq(in, a);
+    add_seq(in, std::vector<uint8_t>(a.begin() + 20, a.begin() + 20 + k));
+    add_seq(in, std::vector<uint8_t>(a.begin() + 3, a.begin() + 3 + k - 1));
+    return in;
+}
+
+// tests/kmer_limits.py: seam_seqs -- the separators' places in the separated layout
+Input seam_input(std::mt19937& rng, int extra) {
+    std::vector<int> seps;
+    for (int i = 0; i < 16; i++) seps.push_back(300 + 41 * i);
+    for (int p : {1000, 1001, 2046, 2047, 2048, 2049, 4095, 4096}) seps.push_back(p);
+    for (int p = 4097; p < 3 * 2048 + extra; p++) seps.push_back(p);
+    std::vector<uint8_t> motif(97), flat(seps.back() + 1);
+    for (auto& c : motif) c = (uint8_t)(rng() % 4);
+    for (size_t i = 0; i < flat.size(); i++) flat[i] = i % 61 ? motif[i % 97] : (uint8_t)(rng() % 5);
+    Input in;
+    int prev = -1;
+    for (int p : seps) {
+        add_seq(in, std::vector<uint8_t>(flat.begin() + prev + 1, flat.begin() + p));
+        prev = p;
+    }
+    if (in.seq_off.back() + (uint64_t)in.M() != (uint64_t)(3 * 2048 + extra)) fail("the seam input's size", 0, extra);
     return in;
 }
 
@@ -196,9 +242,33 @@ int check_input(const Input& in, int k) {
     return cases;
 }
 
+// the constructions of tests/kmer_limits.py
+int limit_cases(std::mt19937& rng) {
+    int cases = 0;
+    for (int k : {81, 82, 108, 109, 2049}) cases += check_input(large_k_input(rng, k), k);
+    for (int extra : {0, 1}) {
+        const Input in = seam_input(rng, extra);
+        for (int k : {1, 8, 25, 28}) cases += check_input(in, k);
+    }
+    {  // exactly one k-mer, between transcripts that have none
+        Input in;
+        add_seq(in, {});
+        add_seq(in, std::vector<uint8_t>(27, 1));
+        add_seq(in, std::vector<uint8_t>(28, 2));
+        add_seq(in, {});
+        cases += check_input(in, 28);
+    }
+    return cases;
+}
+
 }  // namespace
 
 int main(int argc, char* argv[]) {
+    if (argc == 2 && std::string(argv[1]) == "limits") {  // the limit constructions alone
+        std::mt19937 rng(12345);
+        printf("ok %d\n", limit_cases(rng));
+        return 0;
+    }
     if (argc == 2 && std::string(argv[1]) == "pipeline") {
         if (pow5(27) >= (1ull << 63) || key_bits(27) != 63 || key_bits(1) != 3 || key_bits(2) != 5) fail("key_bits", 0, 0);
         if (n_chunks(27) != 1 || n_chunks(28) != 2 || n_chunks(54) != 2 || n_chunks(55) != 3 || chunk_len(60, 2) != 6 || chunk_len(28, 1) != 1)
@@ -210,6 +280,7 @@ int main(int argc, char* argv[]) {
                 const Input in = random_input(rng, letters, 24, 150);
                 cases += check_input(in, k);
             }
+        cases += limit_cases(rng);
         printf("ok %d\n", cases);
         return 0;
     }
@@ -224,6 +295,6 @@ int main(int argc, char* argv[]) {
         }
         return 0;
     }
-    fprintf(stderr, "usage: kmer_check pipeline | kmer_check fasta FILE\n");
+    fprintf(stderr, "usage: kmer_check pipeline | kmer_check limits | kmer_check fasta FILE\n");
     return 64;
 }

@@ -171,6 +171,8 @@ struct HostLayout {
     std::vector<Far> far;
     uint32_t x_slot_base = 0, n_slots = 0;
     bool has_x = false;
+    // what the sort keys say (row_key_of): whole reads that carry the apart bit, and the sum of the anchors the keys hold
+    uint64_t n_apart_rows = 0, anchor_sum = 0;
 };
 
 static void build_layout(HostLayout& H, int M, uint64_t N1, const uint64_t* rp, const int32_t* sid, const double* cp, const double* ncp,
@@ -184,6 +186,8 @@ static void build_layout(HostLayout& H, int M, uint64_t N1, const uint64_t* rp, 
         if (err) { fprintf(stderr, "simt_emu: bad CSR (%d)\n", err); exit(2); }
         if ((int)(key >> (64 - kShapeBits)) == kLongShape) { fprintf(stderr, "simt_emu: rows with more than 256 alignments are not modelled\n"); exit(2); }
         keyed[i] = {key, (uint32_t)i};
+        if (shape_fmt_of_id((int)(key >> (64 - kShapeBits))) != kFmtF64X) H.n_apart_rows += (key >> kKeyApartBit) & 1;
+        H.anchor_sum += (key >> 32) & kKeyMinSidCap;
     }
     std::stable_sort(keyed.begin(), keyed.end());
     H.order.resize(N1);

@@ -119,6 +119,29 @@ def test_check_program_fold_keeps_the_order(checker):
         assert ("batches 1 " in r.stderr) == (not env)
 
 
+def test_check_program_tile_bits(checker):
+    """the sort's end_bit: the bits of the largest tile id, one more at every 2^b + 1 tiles, never none"""
+    n = [1, 2, 3, 4, 5, 2 ** 8, 2 ** 8 + 1, 2 ** 16, 2 ** 16 + 1, 2 ** 32]
+    r = subprocess.run([checker, "tilebits"] + [str(x) for x in n], check=True, capture_output=True, text=True)
+    assert [int(x) for x in r.stdout.split()] == [1, 1, 2, 2, 3, 8, 9, 16, 17, 32]
+    assert all((x - 1).bit_length() <= b for x, b in zip(n, [1, 1, 2, 2, 3, 8, 9, 16, 17, 32]))
+
+
+def test_check_program_fold_past_one_radix_digit(checker):
+    """257 tiles, nine bits: order-sensitive blocks interleaved over tiles 0, 128 and 256 (tests/test_depth_limits_gpu.py's input) --
+    a sort on eight bits would put tile 256's entries among tile 0's"""
+    import test_depth_limits_gpu as lim
+    (n_bases, start, length, w), want, touched = lim.limit_case(257)
+    text = "".join("%d %d %016x\n" % (s, l, b) for s, l, b in zip(start, length, dr.bits(w)))
+    for env in ({}, {"RSEM_DEPTH_BATCH_ITEMS": "100"}):
+        r = subprocess.run([checker, "fold", str(n_bases)], input=text, capture_output=True, text=True, env=dict(os.environ, **env))
+        assert r.returncode == 0, r.stderr[-2000:]
+        got = np.array([int(x, 16) for x in r.stdout.split()], np.uint64)
+        assert np.array_equal(got, dr.bits(want))
+        if not env:
+            assert "batches 1 " in r.stderr and "tiles %d\n" % len(touched) in r.stderr
+
+
 @pytest.fixture(scope="module")
 def programs():
     from rsem_amd import build

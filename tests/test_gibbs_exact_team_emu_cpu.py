@@ -81,6 +81,18 @@ def test_wide_teams_and_the_group_cells(team_256, W):
     _check(team_256, W, CASES[1])
 
 
+@pytest.mark.parametrize("W", [1, 3])
+def test_ids_at_and_above_the_anchor_cap(team_256, W):
+    """the reads of tests/em_id_cap.py as items, M = 2^23 - 1 + 12000 (the input of tests/test_gibbs_id_cap_gpu.py): the team's tables
+    and the count vectors take ids on either side of the sliced layout's anchor cap alike"""
+    import em_id_cap as cap
+    from tools.synth_data import to_gibbs_items
+    d = cap.reads()
+    irp, isid, icp = to_gibbs_items(d)
+    init = np.zeros(d["M"] + 1, np.int32)
+    got, log = _run(team_256, W, d["M"], irp, isid, icp, init, 2, 1001, 100, 1.0)
+    assert isid.max() > cap.CAP + 2 * cap.WINDOW and (W == 1 or " 0 team barriers" not in log)
+    assert np.array_equal(got, _oracle(d["M"], irp, isid, icp, init, 2, 1001, 100, 1.0))
 
 
 @pytest.mark.parametrize("seed", [1, 2, 4, 5, 6])

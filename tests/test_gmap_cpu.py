@@ -126,6 +126,29 @@ def test_check_program_collapse_at_the_seams(checker, n, run):
     assert r.returncode == 0 and r.stdout.startswith("ok "), r.stderr[-2000:]
 
 
+def limit_cases():
+    import gmap_limits as gl
+    return {"exon_cap": lambda: gl.cap_group(1), "exon_cap_mate_2": lambda: gl.cap_group(2), "exon_cap_reads": gl.cap_reads, "high_positions": gl.high_reads,
+            "mixed_launch": lambda: gl.mixed_launch(5, "middle"), "mixed_launch_one_small": lambda: gl.mixed_launch(1, "last"),
+            "last_word_513": lambda: gl.field_group(513, "last_word")[0], "strand_65": lambda: gl.field_group(65, "strand")[0],
+            "mate2_last_word_257": lambda: gl.field_group(257, "mate2_last_word")[0]}
+
+
+@pytest.mark.parametrize("name", ["exon_cap", "exon_cap_mate_2", "exon_cap_reads", "high_positions", "mixed_launch", "mixed_launch_one_small", "last_word_513",
+                                  "strand_65", "mate2_last_word_257"])
+def test_check_program_at_the_limits(checker, name):
+    """tests/gmap_limits.py: 65532 CIGAR words whose last one decides, positions up to 2^31 - 2, wave-sized and longer groups in one batch"""
+    import gmap_limits as gl
+    case = limit_cases()[name]()
+    r = subprocess.run([checker, "fields"], input=gl.fields_input(case), capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout == gl.fields_expected(case) and "batches 1\n" in r.stderr
+    if name.startswith("exon_cap"):
+        assert max(int(l.split()[3]) for l in r.stdout.split("\n") if l and l[0] != "o") == 65532
+    if name == "high_positions":
+        assert max(int(l.split()[4]) for l in r.stdout.split("\n") if l and l[0] != "o") > 65535
+
+
 # ---- the program, before it needs a device ---------------------------------------------------------------------------------------
 
 @pytest.fixture(scope="module")

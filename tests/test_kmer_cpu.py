@@ -61,7 +61,13 @@ def checker(tmp_path_factory):
 def test_check_program_pipeline(checker):
     out = subprocess.run([checker, "pipeline"], check=True, capture_output=True, text=True).stdout
     assert re.fullmatch(r"ok \d+\n", out), out
-    assert int(out.split()[1]) >= 18 * 2
+    assert int(out.split()[1]) >= (18 + 5 + 8 + 1) * 2  # the random inputs, large k, the seams, one k-mer: whole and in batches at least
+
+
+def test_check_program_limits(checker):
+    """the constructions of tests/kmer_limits.py alone: large k, separators on the word, lane and tile seams, one k-mer"""
+    out = subprocess.run([checker, "limits"], check=True, capture_output=True, text=True).stdout
+    assert re.fullmatch(r"ok \d+\n", out) and int(out.split()[1]) >= (5 + 8 + 1) * 2, out
 
 
 @pytest.mark.parametrize("name", ["mixed.fa", "crlf.fa", "tails.fa"])
