@@ -139,6 +139,15 @@ int rsem_em_get_info(const rsem_em_ctx* ctx, const char* key, int64_t* value);
 /* Tuning aid (not part of the reference's surface): one E-step launch of the LANE kernel with per-workgroup start/end
  * timestamps (100 MHz clock), out[2u], out[2u+1] in dispatch order; *n_units_io = capacity in, units written out. */
 int rsem_em_debug_trace(rsem_em_ctx* ctx, const double* theta, unsigned long long* out, uint32_t* n_units_io);
+/* Diagnostic (not part of the reference's surface; it changes nothing in the context): the far entries of the split rows as the
+ * two passes around the E-step kernel read them.  Row order: the entries of the split read in row slot x_slot_base + xs are
+ * [far_ptr[xs], far_ptr[xs + 1]), xs < n_x_slots (empty slots included), in file order; far_sid[e] is an entry's transcript id,
+ * far_src[e] its index into the caller's sid / conprb arrays.  Column order: the same entries sorted by (block of row slots,
+ * transcript id), each with its id, the row slot of its read and its caller index (csc_sid / csc_slot / csc_src).
+ * Two calls: with all six arrays NULL the sizes alone are written (*n_x_slots_io, *n_far_io; all 0 without split rows); with
+ * all six given, *n_x_slots_io and *n_far_io say what the arrays hold (far_ptr one more) and come back as what was written. */
+int rsem_em_debug_far(rsem_em_ctx* ctx, uint32_t* x_slot_base, uint32_t* n_x_slots_io, uint64_t* n_far_io, uint64_t* far_ptr,
+                      int32_t* far_sid, uint64_t* far_src, int32_t* csc_sid, uint32_t* csc_slot, uint64_t* csc_src);
 int rsem_em_destroy(rsem_em_ctx* ctx);
 
 /* One E step + M step: round 1 of 1 of rsem_em_run's kernel sequence, over this context's reads alone (no all-reduce).

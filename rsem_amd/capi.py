@@ -95,6 +95,7 @@ def lib():
         L.rsem_em_set_option.argtypes = [vp, C.c_char_p, C.c_int64]
         L.rsem_em_get_info.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64)]
         L.rsem_em_debug_trace.argtypes = [vp, _f64p, vp, C.POINTER(C.c_uint32)]
+        L.rsem_em_debug_far.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(u64)] + [vp] * 6
         L.rsem_em_destroy.argtypes = [vp]
         L.rsem_em_set_comm.argtypes = [vp, vp]
         L.rsem_em_set_progress.argtypes = [vp, vp, vp]
@@ -242,6 +243,19 @@ class EmContext:
         n = C.c_uint32(len(t))
         _check(lib().rsem_em_debug_trace(self._h, np.ascontiguousarray(theta, np.float64), _ptr(t), C.byref(n)))
         return t[:n.value]
+
+    def debug_far(self):
+        """rsem_em_debug_far: the split rows' far entries in row order (far_ptr[n_x_slots + 1] by row slot - x_slot_base, far_sid,
+        far_src = index into the caller's arrays) and in column order (csc_sid, csc_slot, csc_src); every size 0 without split rows."""
+        base, nxs, nf = C.c_uint32(), C.c_uint32(0), C.c_uint64(0)
+        _check(lib().rsem_em_debug_far(self._h, C.byref(base), C.byref(nxs), C.byref(nf), *([None] * 6)))
+        n = max(nf.value, 1)  # (an empty numpy array may have no address to give)
+        out = dict(far_ptr=np.zeros(nxs.value + 1, np.uint64), far_sid=np.zeros(n, np.int32), far_src=np.zeros(n, np.uint64),
+                   csc_sid=np.zeros(n, np.int32), csc_slot=np.zeros(n, np.uint32), csc_src=np.zeros(n, np.uint64))
+        _check(lib().rsem_em_debug_far(self._h, C.byref(base), C.byref(nxs), C.byref(nf), *[_ptr(a) for a in out.values()]))
+        out = {k: (a if k == "far_ptr" else a[:nf.value]) for k, a in out.items()}
+        out.update(x_slot_base=int(base.value), n_x_slots=int(nxs.value), n_far=int(nf.value))
+        return out
 
     def expected_weights(self, theta, N0, want_weights=True):
         theta = np.ascontiguousarray(theta, np.float64)

@@ -1294,6 +1294,36 @@ int rsem_em_debug_trace(rsem_em_ctx* c, const double* theta, unsigned long long*
     return rc;
 }
 
+// Diagnostic: the split rows' far entries as the two side passes read them (sell_build_far), copied out; nothing in the context changes.
+int rsem_em_debug_far(rsem_em_ctx* c, uint32_t* x_slot_base, uint32_t* n_x_slots_io, uint64_t* n_far_io, uint64_t* far_ptr, int32_t* far_sid,
+                      uint64_t* far_src, int32_t* csc_sid, uint32_t* csc_slot, uint64_t* csc_src) {
+    RSEM_REQUIRE(c && x_slot_base && n_x_slots_io && n_far_io, "NULL argument");
+    RSEM_REQUIRE(c->layout_ok, "there is no layout");
+    const SellLayout& L = c->L;
+    const bool any = L.n_x_rows != 0;  // (no split rows: every size is 0, whatever slots the shape table counted)
+    const uint32_t nxs = any ? L.n_x_slots : 0, cap_xs = *n_x_slots_io;
+    const uint64_t nf = any ? L.n_far : 0, cap_f = *n_far_io;
+    *x_slot_base = any ? L.x_slot_base : 0;
+    *n_x_slots_io = nxs;
+    *n_far_io = nf;
+    if (!far_ptr && !far_sid && !far_src && !csc_sid && !csc_slot && !csc_src) return RSEM_OK;  // first call: the sizes
+    RSEM_REQUIRE(far_ptr && far_sid && far_src && csc_sid && csc_slot && csc_src, "all six arrays or none");
+    RSEM_REQUIRE(cap_xs >= nxs && cap_f >= nf, "the arrays hold fewer row slots or far entries than the layout has");
+    if (!any) { far_ptr[0] = 0; return RSEM_OK; }
+    RSEM_HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    RSEM_HIP_TRY(hipMemcpyAsync(far_ptr, L.d_far_ptr, sizeof(uint64_t) * ((size_t)nxs + 1), hipMemcpyDeviceToHost, st));
+    if (nf) {
+        RSEM_HIP_TRY(hipMemcpyAsync(far_sid, L.d_far_sid, sizeof(int32_t) * nf, hipMemcpyDeviceToHost, st));
+        RSEM_HIP_TRY(hipMemcpyAsync(far_src, L.d_far_src, sizeof(uint64_t) * nf, hipMemcpyDeviceToHost, st));
+        RSEM_HIP_TRY(hipMemcpyAsync(csc_sid, L.d_csc_sid, sizeof(int32_t) * nf, hipMemcpyDeviceToHost, st));
+        RSEM_HIP_TRY(hipMemcpyAsync(csc_slot, L.d_csc_slot, sizeof(uint32_t) * nf, hipMemcpyDeviceToHost, st));
+        RSEM_HIP_TRY(hipMemcpyAsync(csc_src, L.d_csc_src, sizeof(uint64_t) * nf, hipMemcpyDeviceToHost, st));
+    }
+    RSEM_HIP_TRY(hipStreamSynchronize(st));
+    return RSEM_OK;
+}
+
 int rsem_em_destroy(rsem_em_ctx* c) {
     if (!c) return RSEM_OK;
     (void)hipSetDevice(c->device);
