@@ -540,6 +540,63 @@ int rsem_gmap_convert(rsem_gmap* h, int32_t mates, int64_t n_alignments, int64_t
                       uint64_t cigar_cap, uint64_t* out_src, float* out_w /* n_alignments */, rsem_gmap_info* info /* may be NULL */);
 void rsem_gmap_destroy(rsem_gmap* h);
 
+/* ---- FASTA bodies -> bases, segments of bases -> sequences (rsem-extract-reference-transcripts, rsem-synthesis-reference-transcripts,
+ * rsem-preref) ----------------------------------------------------------------------------------------------------------------
+ * A handle owns an output store of store_bytes bytes on the device, the batch of records that is resident, and its buffers.
+ * rsem_refseq_create touches no device memory.  The environment variable RSEM_REFSEQ_STORE_PAD (a whole number of bytes, a
+ * multiple of 16; anything else: RSEM_ERR_INVALID), read there, puts that many device bytes in front of the store: they are
+ * allocated, never written and never read, and count into every address (a few hundred bases on both sides of 2^32).
+ *
+ * rsem_refseq_load replaces the getline / check / += loops over a record's body (extractRef.cpp:336-349, synthesisRef.cpp:175-188:
+ * mode 1, checked; Refs.h:96-102: mode 0, raw).  The host has found the header lines: record r's body is raw[body_lo[r], body_hi[r]),
+ * the bodies ascend and lie apart, what lies between them is not looked at.  Records first, first + 1, ... are taken while the raw
+ * bytes from the first body's start to the last one's end stay within the budget -- a quarter of the free device memory, or the
+ * environment variable RSEM_REFSEQ_BATCH_BYTES (a whole number from 1 on; anything else: RSEM_ERR_INVALID), read at every call; a
+ * record above the budget is a batch of its own -- and *n_taken says how many.  For each of them the device drops the '\n' bytes and
+ * leaves the bases contiguous; n_bases[r] is their number (0 for a record with keep[r] == 0, which is checked but not kept; keep
+ * may be NULL: all are kept).  In checked mode a letter other than A, C, G, T, a, c, g, t becomes N or n by its case (check,
+ * extractRef.cpp:297-303) and bad[r] is the offset into raw of the body's first byte that is no letter, or -1; in raw mode the bytes
+ * stay and bad[r] is -1.  The batch stays resident until the next load.  Refused before anything is uploaded: a record of more than
+ * 2^31 - 1 bases (the reference's coordinates are int).
+ *
+ * rsem_refseq_gather replaces Transcript::extractSeq (Transcript.h:90-117), RefSeqPolicy::convert (RefSeqPolicy.h:11-19),
+ * AlignerRefSeqPolicy::convert and the poly-A append of RefSeq.h:23-28: segment i is len[i] bases of the resident record src[i] (its
+ * index in the load call's arrays) from base first_base[i] (0-based) on, written to the store at dst[i].  flags: 1 the segment is
+ * read backwards through getOpp (utils.h:78-94); 2 upper case, and N for anything but A, C, G, T; 4 N becomes G after that; 8 the
+ * segment is len[i] times 'A' (src and first_base are not looked at).  The destinations must ascend and lie apart (every output byte
+ * has one writer); a segment outside its record or the store is RSEM_ERR_INVALID, before any launch.
+ * rsem_refseq_download copies bytes of the store to the host.  Calls on one handle are serialised. */
+typedef struct rsem_refseq rsem_refseq;
+typedef struct rsem_refseq_info {  /* sums over the handle's calls */
+    uint64_t n_records;
+    uint64_t raw_bytes;        /* uploaded and read twice by the load kernels */
+    uint64_t n_bases;          /* written by the load, kept records only */
+    uint64_t n_segments;
+    uint64_t gathered_bytes;   /* written by the gather (and read, but for the fills) */
+    int32_t n_batches;         /* loads */
+    int32_t n_launches;        /* kernels and library scans: three a load, one a gather */
+    uint64_t batch_bytes;      /* the budget of the last load */
+    uint64_t store_pad;
+    uint64_t device_bytes;     /* held by the handle */
+    double upload_ms;
+    double kernel_ms;
+    double download_ms;
+} rsem_refseq_info;
+#define RSEM_REFSEQ_RAW 0
+#define RSEM_REFSEQ_CHECKED 1
+#define RSEM_REFSEQ_RC 1u
+#define RSEM_REFSEQ_UPPER_N 2u
+#define RSEM_REFSEQ_N2G 4u
+#define RSEM_REFSEQ_FILL 8u
+int rsem_refseq_create(rsem_refseq** out, int device, uint64_t store_bytes);
+int rsem_refseq_load(rsem_refseq* h, int32_t mode, const uint8_t* raw, int64_t n_records, const uint64_t* body_lo, const uint64_t* body_hi,
+                     const uint8_t* keep /* may be NULL */, int64_t first, int64_t* n_taken, uint64_t* n_bases /* n_records */, int64_t* bad /* n_records */);
+int rsem_refseq_gather(rsem_refseq* h, int64_t n_segments, const int64_t* src, const uint32_t* first_base, const uint32_t* len, const uint64_t* dst,
+                       const uint32_t* flags);
+int rsem_refseq_download(rsem_refseq* h, uint64_t offset, uint64_t bytes, uint8_t* out);
+int rsem_refseq_get_info(rsem_refseq* h, rsem_refseq_info* info);
+void rsem_refseq_destroy(rsem_refseq* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,13 @@ class GmapInfo(C.Structure):
                 ("upload_ms", C.c_double), ("kernel_ms", C.c_double)]
 
 
+class RefseqInfo(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("raw_bytes", C.c_uint64), ("n_bases", C.c_uint64), ("n_segments", C.c_uint64),
+                ("gathered_bytes", C.c_uint64), ("n_batches", C.c_int32), ("n_launches", C.c_int32), ("batch_bytes", C.c_uint64),
+                ("store_pad", C.c_uint64), ("device_bytes", C.c_uint64), ("upload_ms", C.c_double), ("kernel_ms", C.c_double),
+                ("download_ms", C.c_double)]
+
+
 class EmProfile(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("estep_ms_sum", C.c_double), ("estep_launches", C.c_int32),
                 ("rounds", C.c_int32), ("algorithmic_bytes_per_round", C.c_uint64)]
@@ -135,6 +142,13 @@ def lib():
         L.rsem_gmap_convert.argtypes = [vp, i32, C.c_int64, C.c_int64] + [vp] * 14 + [u64, vp, vp, vp]
         L.rsem_gmap_destroy.argtypes = [vp]
         L.rsem_gmap_destroy.restype = None
+        L.rsem_refseq_create.argtypes = [C.POINTER(vp), ci, u64]
+        L.rsem_refseq_load.argtypes = [vp, i32, vp, C.c_int64, vp, vp, vp, C.c_int64, C.POINTER(C.c_int64), vp, vp]
+        L.rsem_refseq_gather.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp]
+        L.rsem_refseq_download.argtypes = [vp, u64, u64, vp]
+        L.rsem_refseq_get_info.argtypes = [vp, vp]
+        L.rsem_refseq_destroy.argtypes = [vp]
+        L.rsem_refseq_destroy.restype = None
         _lib = L
     return _lib
 
@@ -582,6 +596,78 @@ class Gmap:
     def close(self):
         if self.h:
             lib().rsem_gmap_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+REFSEQ_RAW, REFSEQ_CHECKED = 0, 1
+REFSEQ_RC, REFSEQ_UPPER_N, REFSEQ_N2G, REFSEQ_FILL = 1, 2, 4, 8
+
+
+class Refseq:
+    """rsem_refseq: FASTA bodies -> bases (load) and segments of bases -> an output store (gather) of the reference-preparation
+    programs.  store_bytes: the size of the store."""
+
+    def __init__(self, store_bytes, device=0):
+        self.store_bytes = int(store_bytes)
+        self.h = C.c_void_p()
+        _check(lib().rsem_refseq_create(C.byref(self.h), device, self.store_bytes))
+
+    def load(self, mode, raw, body_lo, body_hi, keep=None, first=0):
+        """rsem_refseq_load from record `first` on.  Returns (n_taken, n_bases, bad): the arrays have an element per record of the call,
+        those of the records taken are filled."""
+        self._raw = np.frombuffer(raw, np.uint8) if isinstance(raw, (bytes, bytearray)) else np.ascontiguousarray(raw, np.uint8)
+        lo, hi = np.ascontiguousarray(body_lo, np.uint64), np.ascontiguousarray(body_hi, np.uint64)
+        assert len(lo) == len(hi)
+        kp = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+        n_bases, bad = np.zeros(max(len(lo), 1), np.uint64), np.full(max(len(lo), 1), -1, np.int64)
+        taken = C.c_int64(0)
+        _check(lib().rsem_refseq_load(self.h, mode, _ptr(self._raw), len(lo), _ptr(lo), _ptr(hi), _ptr(kp), first, C.byref(taken), _ptr(n_bases), _ptr(bad)))
+        return taken.value, n_bases[:len(lo)], bad[:len(lo)]
+
+    def gather(self, src, first_base, length, dst, flags):
+        src = np.ascontiguousarray(src, np.int64)
+        first_base, length, flags = (np.ascontiguousarray(x, np.uint32) for x in (first_base, length, flags))
+        dst = np.ascontiguousarray(dst, np.uint64)
+        assert len(src) == len(first_base) == len(length) == len(dst) == len(flags)
+        _check(lib().rsem_refseq_gather(self.h, len(src), _ptr(src), _ptr(first_base), _ptr(length), _ptr(dst), _ptr(flags)))
+
+    def run(self, mode, raw, body_lo, body_hi, segments, keep=None):
+        """Every record through load, batch after batch, each batch followed by the segments (src, first_base, len, dst, flags) that
+        read from it, in the order given; the fills go with the first batch.  Returns (n_bases, bad)."""
+        n = len(body_lo)
+        seg = np.array(segments, np.int64).reshape(-1, 5)
+        first, n_bases, bad = 0, np.zeros(n, np.uint64), np.full(n, -1, np.int64)
+        while first < n:
+            taken, nb, bd = self.load(mode, raw, body_lo, body_hi, keep, first)
+            n_bases[first:first + taken], bad[first:first + taken] = nb[first:first + taken], bd[first:first + taken]
+            fill = (seg[:, 4] & REFSEQ_FILL) != 0
+            here = (fill & (first == 0)) | (~fill & (seg[:, 0] >= first) & (seg[:, 0] < first + taken))
+            g = seg[here]
+            if len(g):
+                self.gather(g[:, 0], g[:, 1], g[:, 2], g[:, 3], g[:, 4])
+            first += taken
+        return n_bases, bad
+
+    def download(self, offset=0, nbytes=None):
+        nbytes = self.store_bytes - offset if nbytes is None else nbytes
+        out = np.zeros(max(nbytes, 1), np.uint8)
+        _check(lib().rsem_refseq_download(self.h, offset, nbytes, _ptr(out)))
+        return out[:nbytes].tobytes()
+
+    def info(self):
+        info = RefseqInfo()
+        _check(lib().rsem_refseq_get_info(self.h, C.addressof(info)))
+        return {f: getattr(info, f) for f, _ in RefseqInfo._fields_}
+
+    def close(self):
+        if self.h:
+            lib().rsem_refseq_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
