@@ -597,6 +597,92 @@ int rsem_refseq_download(rsem_refseq* h, uint64_t offset, uint64_t bytes, uint8_
 int rsem_refseq_get_info(rsem_refseq* h, rsem_refseq_info* info);
 void rsem_refseq_destroy(rsem_refseq* h);
 
+/* ---- the checks of a name-grouped alignment file (rsem-sam-validator, rsem-get-unique) -----------------------------------------
+ * rsem_alncheck_create keeps target_len (bam_hdr_t::target_len, samValidator.cpp:45,143) and touches no device.
+ *
+ * rsem_alncheck_push is a stream: the records of one push continue those of the pushes before.  It replaces the loop of
+ * samValidator.cpp:82-183 with check_read (:26-59).  Record i has the name names[name_off[i] .. name_off[i + 1]) (no NUL), its BAM
+ * fields flag, tid, pos, isize, l_qseq, and the CIGAR words cigar[cigar_off[i] .. cigar_off[i + 1]).  The first record of the first push
+ * fixes the mode (:91): flag & 1 set means paired.  A unit is one record, or in paired mode the records 2k and 2k + 1 of the file (:101);
+ * a push in paired mode holds an even number of records unless `last` is set.  Per unit, the first check that fails, in the
+ * reference's order (:93-164): MIXED, ONE_MATE (no second record, other canonical name, second not flagged paired), SAME_MATE_NUMBER,
+ * ONE_MATE_ALIGNED, then with both mates aligned and read 1 first DISCORDANT, SAME_STRAND, PAIR_BOUNDARY (the mate of smaller pos:
+ * pos >= 0 && pos + |isize| <= target_len, in 64 bits), check_read of read 1, check_read of read 2; single-end, if mapped, check_read.
+ * check_read (:26-59): the first offending CIGAR operation in CIGAR order -- CIGAR_SKIP for N, CIGAR_INDEL for I or D, CIGAR_CLIP for
+ * S, H or P -- then BOUNDARY: pos < 0 or bam_endpos of htslib 1.3 (sam.c:336-342: pos + the reference-consuming lengths, pos + 1 for a
+ * record without CIGAR) above target_len[tid].  After the unit's own checks those of its group (:166-178); a unit's name is its first
+ * record's canonical name, the bytes before the first of " \t\n\r\f\v" (sam_utils.h:45,54-61; cut on the device): a unit whose name
+ * differs from the unit before opens a group, NOT_GROUPED if an earlier group of the file has exactly that name (the std::set `used`,
+ * :22,167-169); a unit that continues a group repeats the l_qseq of the unit before (read 1's and read 2's in paired mode), else
+ * DIFFERENT_LENGTHS (:176).  The verdict is the failing unit of smallest index: where the reference stops.  Once a verdict with
+ * code != 0 has been returned, or after a push with `last`, further pushes are refused (RSEM_ERR_STATE).
+ * NOT_GROUPED is exact: every group's name stays on the device (its bytes and 16 bytes a group: a 64-bit hash and where the name
+ * lies), a batch's groups as a run sorted by (hash, group); equal hashes are settled by comparing the bytes.  When they no longer fit:
+ * RSEM_ERR_NOMEM, with what is resident kept.
+ * Checked before a device is touched (RSEM_ERR_INVALID): a NULL handle or verdict, negative counts, name_off / cigar_off that do not
+ * start at 0 and ascend, a name of 0 or more than 254 bytes or one that starts with white space (the reference's assert at :175),
+ * more than 65535 CIGAR operations, l_qseq < 1 (its assert at :86,107), a mapped record whose tid is outside the targets (:45 reads
+ * outside its arrays there), an odd number of paired-end records without `last`.
+ * The environment variables RSEM_ALNCHECK_BATCH_ITEMS (a whole number >= 1) and RSEM_ALNCHECK_HASH_BITS (1 .. 64: only that many bits
+ * of the hash are kept -- collisions on purpose), read at every call (anything else: RSEM_ERR_INVALID), replace the batch budget of
+ * 2^22 records and the hash width: test knobs, the verdicts do not depend on them.
+ *
+ * rsem_alncheck_unique is stateless and takes whole groups; it replaces output() of getUnique.cpp:25-30 and the grouping of :55-65:
+ * groups are runs of equal RAW names; keep[i] = 1 iff no record of i's group has flag & 4 and the group has 2 records where its first
+ * has flag & 1, else 1.  It takes the batch knob (the end of a batch moves behind the group it would cut). */
+#define RSEM_ALNCHECK_OK 0
+#define RSEM_ALNCHECK_MIXED 1
+#define RSEM_ALNCHECK_ONE_MATE 2
+#define RSEM_ALNCHECK_SAME_MATE_NUMBER 3
+#define RSEM_ALNCHECK_ONE_MATE_ALIGNED 4
+#define RSEM_ALNCHECK_DISCORDANT 5
+#define RSEM_ALNCHECK_SAME_STRAND 6
+#define RSEM_ALNCHECK_PAIR_BOUNDARY 7
+#define RSEM_ALNCHECK_CIGAR_SKIP 8
+#define RSEM_ALNCHECK_CIGAR_INDEL 9
+#define RSEM_ALNCHECK_CIGAR_CLIP 10
+#define RSEM_ALNCHECK_BOUNDARY 11
+#define RSEM_ALNCHECK_NOT_GROUPED 12
+#define RSEM_ALNCHECK_DIFFERENT_LENGTHS 13
+typedef struct rsem_alncheck rsem_alncheck;
+typedef struct rsem_alncheck_verdict {
+    int32_t code;              /* 0 = nothing wrong so far, else RSEM_ALNCHECK_* */
+    int32_t mate;              /* which record of the unit the message names (0 / 1) */
+    int64_t unit_record;       /* index in this push of the failing unit's first record; -1 if code == 0 */
+    uint64_t units_ok;         /* units counted before the stop (the reference's cnt): this push only */
+    uint32_t cigar_op;         /* the offending operation's letter for the CIGAR codes */
+    int32_t paired;            /* the mode: 0 / 1, -1 before the first record */
+    uint64_t n_records;        /* of this push */
+    uint64_t n_units;
+    uint64_t n_groups;         /* opened by this push */
+    uint64_t resident_groups;  /* of the handle */
+    uint64_t resident_name_bytes;
+    int32_t n_batches;
+    int32_t n_launches;        /* kernels and library calls: three a batch, five where it opens a group */
+    uint64_t batch_items;      /* the budget in force */
+    uint64_t device_bytes;     /* held by the handle after the call */
+    double upload_ms;
+    double kernel_ms;          /* the batches' kernels, scans and sorts */
+} rsem_alncheck_verdict;
+typedef struct rsem_alncheck_info {
+    uint64_t n_records;
+    uint64_t n_groups;
+    uint64_t n_kept;
+    int32_t n_batches;
+    int32_t n_launches;        /* three a batch */
+    uint64_t batch_items;
+    uint64_t device_bytes;     /* held during the call */
+    double upload_ms;
+    double kernel_ms;
+} rsem_alncheck_info;
+int rsem_alncheck_create(rsem_alncheck** out, int device, int32_t n_targets, const uint32_t* target_len);
+int rsem_alncheck_push(rsem_alncheck* h, int64_t n_records, const uint64_t* name_off /* n + 1 */, const uint8_t* names, const uint32_t* flag,
+                       const int32_t* tid, const int32_t* pos, const int32_t* isize, const int32_t* l_qseq, const uint64_t* cigar_off /* n + 1 */,
+                       const uint32_t* cigar, int32_t last, rsem_alncheck_verdict* v);
+void rsem_alncheck_destroy(rsem_alncheck* h);
+int rsem_alncheck_unique(int device, int64_t n_records, const uint64_t* name_off /* n + 1 */, const uint8_t* names, const uint32_t* flag,
+                         uint8_t* keep /* n_records */, rsem_alncheck_info* info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,6 +68,18 @@ class RefseqInfo(C.Structure):
                 ("download_ms", C.c_double)]
 
 
+class AlncheckVerdict(C.Structure):
+    _fields_ = [("code", C.c_int32), ("mate", C.c_int32), ("unit_record", C.c_int64), ("units_ok", C.c_uint64), ("cigar_op", C.c_uint32), ("paired", C.c_int32),
+                ("n_records", C.c_uint64), ("n_units", C.c_uint64), ("n_groups", C.c_uint64), ("resident_groups", C.c_uint64), ("resident_name_bytes", C.c_uint64),
+                ("n_batches", C.c_int32), ("n_launches", C.c_int32), ("batch_items", C.c_uint64), ("device_bytes", C.c_uint64),
+                ("upload_ms", C.c_double), ("kernel_ms", C.c_double)]
+
+
+class AlncheckInfo(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_groups", C.c_uint64), ("n_kept", C.c_uint64), ("n_batches", C.c_int32), ("n_launches", C.c_int32),
+                ("batch_items", C.c_uint64), ("device_bytes", C.c_uint64), ("upload_ms", C.c_double), ("kernel_ms", C.c_double)]
+
+
 class EmProfile(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("estep_ms_sum", C.c_double), ("estep_launches", C.c_int32),
                 ("rounds", C.c_int32), ("algorithmic_bytes_per_round", C.c_uint64)]
@@ -149,6 +161,11 @@ def lib():
         L.rsem_refseq_get_info.argtypes = [vp, vp]
         L.rsem_refseq_destroy.argtypes = [vp]
         L.rsem_refseq_destroy.restype = None
+        L.rsem_alncheck_create.argtypes = [C.POINTER(vp), ci, i32, vp]
+        L.rsem_alncheck_push.argtypes = [vp, C.c_int64] + [vp] * 9 + [i32, vp]
+        L.rsem_alncheck_destroy.argtypes = [vp]
+        L.rsem_alncheck_destroy.restype = None
+        L.rsem_alncheck_unique.argtypes = [ci, C.c_int64, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -675,3 +692,53 @@ class Refseq:
             self.close()
         except Exception:
             pass
+
+
+(ALNCHECK_OK, ALNCHECK_MIXED, ALNCHECK_ONE_MATE, ALNCHECK_SAME_MATE_NUMBER, ALNCHECK_ONE_MATE_ALIGNED, ALNCHECK_DISCORDANT, ALNCHECK_SAME_STRAND,
+ ALNCHECK_PAIR_BOUNDARY, ALNCHECK_CIGAR_SKIP, ALNCHECK_CIGAR_INDEL, ALNCHECK_CIGAR_CLIP, ALNCHECK_BOUNDARY, ALNCHECK_NOT_GROUPED, ALNCHECK_DIFFERENT_LENGTHS) = range(14)
+
+
+class Alncheck:
+    """rsem_alncheck: the checks of rsem-sam-validator as a stream of pushes.  target_len: the header's sequence lengths."""
+
+    def __init__(self, target_len, device=0):
+        self.target_len = np.ascontiguousarray(target_len, np.uint32)
+        self.h = C.c_void_p()
+        _check(lib().rsem_alncheck_create(C.byref(self.h), device, len(self.target_len), _ptr(self.target_len)))
+
+    def push(self, name_off, names, flag, tid, pos, isize, l_qseq, cigar_off, cigar, last=False):
+        """rsem_alncheck_push.  Returns the verdict as a dict."""
+        name_off, cigar_off = np.ascontiguousarray(name_off, np.uint64), np.ascontiguousarray(cigar_off, np.uint64)
+        names = np.frombuffer(names, np.uint8) if isinstance(names, (bytes, bytearray)) else np.ascontiguousarray(names, np.uint8)
+        flag, cigar = np.ascontiguousarray(flag, np.uint32), np.ascontiguousarray(cigar, np.uint32)
+        tid, pos, isize, l_qseq = (np.ascontiguousarray(x, np.int32) for x in (tid, pos, isize, l_qseq))
+        n = len(flag)
+        assert len(name_off) == n + 1 and len(cigar_off) == n + 1 and len(tid) == n and len(pos) == n and len(isize) == n and len(l_qseq) == n
+        v = AlncheckVerdict()
+        _check(lib().rsem_alncheck_push(self.h, n, _ptr(name_off), _ptr(names), _ptr(flag), _ptr(tid), _ptr(pos), _ptr(isize), _ptr(l_qseq), _ptr(cigar_off), _ptr(cigar),
+                                        1 if last else 0, C.addressof(v)))
+        return {f: getattr(v, f) for f, _ in AlncheckVerdict._fields_}
+
+    def close(self):
+        if self.h:
+            lib().rsem_alncheck_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def alncheck_unique(name_off, names, flag, device=0):
+    """rsem_alncheck_unique: (keep, info) -- per record whether rsem-get-unique writes it."""
+    name_off = np.ascontiguousarray(name_off, np.uint64)
+    names = np.frombuffer(names, np.uint8) if isinstance(names, (bytes, bytearray)) else np.ascontiguousarray(names, np.uint8)
+    flag = np.ascontiguousarray(flag, np.uint32)
+    n = len(flag)
+    assert len(name_off) == n + 1
+    keep = np.zeros(max(n, 1), np.uint8)
+    info = AlncheckInfo()
+    _check(lib().rsem_alncheck_unique(device, n, _ptr(name_off), _ptr(names), _ptr(flag), _ptr(keep), C.addressof(info)))
+    return keep[:n], {f: getattr(info, f) for f, _ in AlncheckInfo._fields_}

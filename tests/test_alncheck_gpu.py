@@ -1,0 +1,291 @@
+"""The checks of rsem-sam-validator and rsem-get-unique on the GPU (rsem_amd/csrc/alncheck.hip through capi.Alncheck / capi.alncheck_unique,
+and the two programs) against the Python restatement (tests/alncheck_ref.py) and what the unmodified reference programs said and wrote
+(tests/golden/alncheck/).  There are no tolerances: verdicts, keep flags and files are compared for equality.
+
+A lane takes a unit, a wave reduces to one atomic, a workgroup has 256 lanes: every stream is a few hundred units and puts its events
+on lanes 0, 63, 64, 255, 256 and the last one; batches and pushes are cut through groups and between the events."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import alncheck_ref as ar
+import gmap_ref as gr
+from alncheck_ref import GET_UNIQUE, GOLDEN, VALIDATOR, pair, rec
+
+pytestmark = pytest.mark.gpu
+
+TLEN = [100, 200, 50]
+SEAMS = [0, 63, 64, 255, 256]
+N_UNITS = 600
+
+
+def check(recs, cuts=(), tlen=TLEN):
+    """the library's verdict equals the restatement's; returns (verdict, pushes)"""
+    got, pushes = ar.device_verdict(recs, tlen, cuts)
+    assert got == ar.verdict(recs, tlen)
+    return got, pushes
+
+
+def stream(n, paired, name="u%d"):
+    """n valid units, each a group of its own"""
+    return [r for k in range(n) for r in (pair(name % k, k % 2, 5, 30) if paired else [rec(name % k, 0, k % 3, k % 40)])]
+
+
+def set_unit(recs, paired, u, unit):
+    m = 2 if paired else 1
+    recs[u * m:(u + 1) * m] = unit
+
+
+# ---- the fixtures --------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("ci", ar.inputs(ar.validator_cases()), ids=ar.input_id)
+def test_validator_prints_the_recorded_stdout(ci):
+    assert os.path.exists(VALIDATOR), "rsem-sam-validator was not built"
+    case, path = ci
+    extra = ["-p", "4", "--device", "0"] if path.endswith(".bam") else []
+    r = subprocess.run([VALIDATOR, path] + extra, capture_output=True)
+    assert r.returncode == 0 and r.stdout == ar.recorded(case, ".stdout"), r.stderr
+
+
+@pytest.mark.parametrize("ci", ar.inputs(ar.unique_cases()), ids=ar.input_id)
+def test_get_unique_writes_the_recorded_file(tmp_path, ci):
+    assert os.path.exists(GET_UNIQUE), "rsem-get-unique was not built"
+    case, path = ci
+    out = os.path.join(str(tmp_path), "out.bam")
+    r = subprocess.run([GET_UNIQUE, "4" if path.endswith(".bam") else "1", path, out] + (["--device", "0"] if path.endswith(".bam") else []), capture_output=True)
+    assert r.returncode == 0 and r.stdout == b"done!\n", r.stderr
+    assert gr.bgzf_inflate(open(out, "rb").read()) == ar.recorded(case, ".unique")
+
+
+@pytest.mark.parametrize("env", [{"RSEM_ALNCHECK_BATCH_ITEMS": "1", "RSEM_ALNCHECK_HASH_BITS": "1"}, {"RSEM_ALNCHECK_BATCH_ITEMS": "3", "RSEM_HIP_BAM_CHUNK": "200"}],
+                         ids=["a_batch_per_unit_one_hash_bit", "groups_and_pairs_cut_by_super_chunks"])
+@pytest.mark.parametrize("name", ["valid_pe.bam", "aba_pe.sam", "different_lengths_swapped.bam", "uniq_pe.bam", "uniq_se.sam"])
+def test_programs_batches_and_super_chunks_change_nothing(tmp_path, name, env):
+    case, path, out = name.split(".")[0], os.path.join(GOLDEN, name), os.path.join(str(tmp_path), "out.bam")
+    if case in ar.validator_cases():
+        r = subprocess.run([VALIDATOR, path, "-p", "2"], capture_output=True, env=dict(os.environ, **env))
+        assert r.returncode == 0 and r.stdout == ar.recorded(case, ".stdout"), r.stderr
+    if case in ar.unique_cases():
+        subprocess.run([GET_UNIQUE, "2", path, out], check=True, capture_output=True, env=dict(os.environ, **env))
+        assert gr.bgzf_inflate(open(out, "rb").read()) == ar.recorded(case, ".unique")
+
+
+@pytest.mark.parametrize("case", ar.validator_cases())
+def test_every_code_alone(case):
+    """the fixtures' records through the library: each code, its mate and its operation"""
+    targets, recs = ar.load(os.path.join(GOLDEN, case + ".bam"))
+    got, pushes = check(recs, tlen=[l for _, l in targets])
+    assert ar.message(got, recs, targets).encode() in ar.recorded(case, ".stdout")
+    if recs:
+        assert pushes[0]["n_batches"] == 1 and pushes[0]["upload_ms"] > 0 and pushes[0]["kernel_ms"] > 0 and pushes[0]["device_bytes"] > 0
+
+
+# ---- failing units -------------------------------------------------------------------------------------------------------------------
+
+def failing_unit(kind, paired, k):
+    name = "bad%d" % k
+    if paired:
+        return {"boundary": pair(name, 0, 5, 95), "cigar": pair(name, 0, 5, 30, cigar1=[(4, "M"), (2, "I"), (4, "M")]), "strand": [rec(name, 0x41, 0, 5), rec(name, 0x81, 0, 30)],
+                "mate": [rec(name, 0x41 | 0x20, 0, 5), rec(name, 0x41 | 0x10, 0, 30)]}[kind]
+    return {"boundary": [rec(name, 0, 0, 95)], "cigar": [rec(name, 0, 0, 5, 10, [(2, "S"), (8, "M")])], "strand": [rec(name, 0x1, 0, 5)], "mate": [rec(name, 0, 0, -1)]}[kind]
+
+
+@pytest.mark.parametrize("paired", [0, 1], ids=["se", "pe"])
+@pytest.mark.parametrize("where", ["one_launch", "batches_of_100", "batches_of_1", "pushes"])
+def test_the_smaller_of_two_failing_units_wins(monkeypatch, paired, where):
+    """two failing units on lanes of different waves, workgroups, batches and pushes: the verdict is the first one's"""
+    if where.startswith("batches"):
+        monkeypatch.setenv("RSEM_ALNCHECK_BATCH_ITEMS", where.split("_")[-1])
+    places = SEAMS + [N_UNITS - 1]
+    m = 2 if paired else 1
+    for i, (a, b) in enumerate(zip(places, places[1:])):
+        recs = stream(N_UNITS, paired)
+        set_unit(recs, paired, a, failing_unit(["boundary", "cigar", "strand", "mate"][i % 4], paired, a))
+        set_unit(recs, paired, b, failing_unit(["cigar", "mate", "boundary", "strand"][i % 4], paired, b))
+        cuts = [m * (a + 1)] if where == "pushes" and a + 1 < b else ([m * b] if where == "pushes" else [])
+        got, pushes = check(recs, cuts)
+        assert got.unit_record == m * a and got.units_ok == a and got.code != ar.OK
+        if where == "batches_of_100" and a >= 200 // m:
+            assert pushes[0]["n_batches"] == (m * a) // 100 + 1  # nothing is run behind the batch that fails
+
+
+def test_a_failing_last_unit_and_none():
+    for paired in (0, 1):
+        recs = stream(N_UNITS, paired)
+        got, pushes = check(recs)
+        assert got.code == ar.OK and got.units_ok == N_UNITS and pushes[0]["n_groups"] == N_UNITS and pushes[0]["resident_groups"] == N_UNITS
+        set_unit(recs, paired, N_UNITS - 1, failing_unit("boundary", paired, 0))
+        assert check(recs)[0].units_ok == N_UNITS - 1
+
+
+# ---- groups ----------------------------------------------------------------------------------------------------------------------------
+
+SIZES = [1, 2, 63, 64, 65, 256, 257]
+
+
+def groups(paired, sizes=SIZES):
+    recs, starts = [], []
+    for g, n in enumerate(sizes):
+        starts.append(len(recs))
+        for k in range(n):
+            recs += pair("g%d" % g, k % 2, 5, 30, 10, 12, second_first=k % 3 == 1) if paired else [rec("g%d x%d" % (g, k), 0 if k % 2 else 4, k % 3 if k % 2 else -1, 5)]
+    return recs, starts
+
+
+@pytest.mark.parametrize("paired", [0, 1], ids=["se", "pe"])
+@pytest.mark.parametrize("budget", [None, 1, 7, 64])
+def test_groups_of_every_size_across_batches(monkeypatch, paired, budget):
+    if budget:
+        monkeypatch.setenv("RSEM_ALNCHECK_BATCH_ITEMS", str(budget))
+    recs, _ = groups(paired)
+    got, pushes = check(recs)
+    n_units = sum(SIZES)
+    assert got.code == ar.OK and got.units_ok == n_units and pushes[0]["n_groups"] == len(SIZES) and pushes[0]["batch_items"] == (budget or ar.DEFAULT_BATCH_ITEMS)
+    per = budget or ar.DEFAULT_BATCH_ITEMS
+    per += per & 1 if paired else 0  # whole units: the budget rounds up to a pair
+    assert pushes[0]["n_batches"] == -(-len(recs) // per)
+
+
+@pytest.mark.parametrize("paired", [0, 1], ids=["se", "pe"])
+def test_groups_across_pushes_and_different_lengths_behind_every_edge(monkeypatch, paired):
+    """the group of 257 units goes over a batch edge, a push edge and three pushes; then the unit just behind each edge has another length"""
+    monkeypatch.setenv("RSEM_ALNCHECK_BATCH_ITEMS", "128")
+    m = 2 if paired else 1
+    recs, starts = groups(paired)
+    big = starts[-1]  # the first record of the group of 257
+    cuts3 = [big + m * 50, big + m * 200]
+    for cuts in ([], [big + m * 100], cuts3, [m * 1], [starts[2]]):
+        got, pushes = check(recs, cuts)
+        assert got.code == ar.OK and sum(p["n_groups"] for p in pushes) == len(SIZES)
+    edges = [128 // m * m // m, (big + m * 50) // m, (big + m * 200) // m, sum(SIZES) - 1]  # units: behind the first batch edge, behind either push edge, the last
+    for u in edges:
+        other = list(recs)
+        r0 = u * m
+        if paired:
+            k = 1 if other[r0].flag & 0x40 else 0  # read 2's length
+            other[r0 + k] = other[r0 + k]._replace(lq=13, cigar=(13 << 4,))
+        else:
+            other[r0] = other[r0]._replace(lq=11, cigar=(11 << 4,))
+        got, _ = check(other, cuts3)
+        if ar.canonical(recs[r0].name) == ar.canonical(recs[r0 - m].name):
+            assert (got.code, got.unit_record) == (ar.DIFFERENT_LENGTHS, r0)
+
+
+# ---- names -----------------------------------------------------------------------------------------------------------------------------
+
+def name_set():
+    base = [bytes([97 + (k * 7 + i) % 26 for i in range(n)]) for k, n in enumerate([1, 3, 4, 5, 7, 8, 9, 15, 16, 17, 254])]
+    out = list(base)
+    out += [b[:-1] + bytes([b[-1] ^ 1]) for b in base]           # the last byte only
+    out += [b[:-1] for b in base if len(b) > 1]                   # a prefix of another
+    return [n for i, n in enumerate(out) if n not in out[:i]]
+
+
+@pytest.mark.parametrize("bits", [64, 3, 1])
+def test_names_of_every_length_are_told_apart_and_found_again(monkeypatch, bits):
+    monkeypatch.setenv("RSEM_ALNCHECK_HASH_BITS", str(bits))
+    names = name_set()
+    assert {len(n) for n in names} >= {1, 3, 4, 5, 7, 8, 9, 15, 16, 17, 254, 253}
+    recs = [rec(n) for n in names]
+    got, pushes = check(recs)
+    assert got.code == ar.OK and pushes[0]["n_groups"] == len(names) and pushes[0]["resident_name_bytes"] == sum(len(n) for n in names)
+    for k in range(0, len(names) - 1):
+        got, _ = check(recs + [rec(names[k])], [len(recs)] if k % 2 else [])
+        assert (got.code, got.unit_record) == (ar.NOT_GROUPED, len(recs))
+
+
+def test_names_are_cut_at_the_first_white_space():
+    recs = [rec("abc one"), rec("abc\ttwo"), rec("abc"), rec("abcd"), rec("abc\x0bthree")]  # three units of read abc, then abcd, then abc again
+    got, _ = check(recs)
+    assert (got.code, got.unit_record, got.units_ok) == (ar.NOT_GROUPED, 4, 4)
+    got, pushes = check(recs[:4] + [rec("abcd\rx"), rec("ab c")])
+    assert got.code == ar.OK and pushes[0]["n_groups"] == 3 and pushes[0]["resident_name_bytes"] == 3 + 4 + 2
+    got, _ = check(pair("p one", name2="p two") + pair("p") + pair("q", name2="q2"))
+    assert (got.code, got.unit_record) == (ar.ONE_MATE, 4)
+
+
+# ---- repeated names --------------------------------------------------------------------------------------------------------------------
+
+def repeats():
+    """(records, cuts) of streams of 300 reads with one name coming back"""
+    base = stream(300, 0, "read%d")
+    out = {"distance_2": (base[:150] + [rec("read148")] + base[150:], []), "beyond_a_batch": (base[:200] + [rec("read3")] + base[200:], []),
+           "in_another_push": (base + [rec("read170")], [250]), "the_first_name_last": (base + [rec("read0")], []),
+           "the_first_name_last_in_a_push_of_its_own": (base + [rec("read0")], [100, 300]), "none": (base, [120])}
+    pe = stream(150, 1, "pair%d")
+    out["pairs_distance_2"] = (pe[:100] + pair("pair48") + pe[100:], [])
+    out["pairs_in_another_push"] = (pe + pair("pair149")[:0] + pair("pair7"), [200])
+    return out
+
+
+@pytest.mark.parametrize("budget", [None, 1, 7])
+@pytest.mark.parametrize("bits", [None, 64, 3, 1])
+def test_a_name_that_comes_back(monkeypatch, bits, budget):
+    """with one and three hash bits every bisection lands in a crowd of equal hashes: the bytes decide, and the verdicts stay the same"""
+    if bits:
+        monkeypatch.setenv("RSEM_ALNCHECK_HASH_BITS", str(bits))
+    if budget:
+        monkeypatch.setenv("RSEM_ALNCHECK_BATCH_ITEMS", str(budget))
+    for name, (recs, cuts) in repeats().items():
+        got, _ = check(recs, cuts)
+        assert (got.code == ar.OK) == (name == "none"), name
+        if name != "none":
+            assert got.code == ar.NOT_GROUPED, name
+
+
+# ---- paired mode -----------------------------------------------------------------------------------------------------------------------
+
+def test_paired_mode_odd_counts_and_swapped_mates():
+    recs = stream(100, 1)
+    got, _ = check(recs + pair("lonely")[:1])
+    assert (got.code, got.unit_record, got.units_ok) == (ar.ONE_MATE, 200, 100)
+    got, _ = check(recs + pair("lonely")[:1], [100])
+    assert (got.code, got.unit_record) == (ar.ONE_MATE, 200)
+    got, _ = check(recs + [rec("single")])  # the last record disagrees with the mode before anyone asks for its mate
+    assert (got.code, got.unit_record) == (ar.MIXED, 200)
+    swapped = [r for k in range(130) for r in pair("s%d" % (k // 2), 1, 100, 150, 40, 50, second_first=k % 2 == 1)]
+    assert check(swapped)[0].code == ar.OK
+    # units are the records 2k and 2k + 1 whatever their names: a record too many shifts every pair behind it
+    got, _ = check(recs[:64 * 2] + pair("extra")[:1] + recs[64 * 2:])
+    assert (got.code, got.unit_record) == (ar.ONE_MATE, 128)
+
+
+# ---- rsem_alncheck_unique --------------------------------------------------------------------------------------------------------------
+
+def unique_stream(paired):
+    recs = []
+    for g, n in enumerate(SIZES + [1, 2, 2, 1, 3]):
+        for k in range(n):
+            flag = (0x41 if k % 2 == 0 else 0x81) if paired else 0
+            recs.append(rec("g%d" % g, flag))
+    # unmapped records first and last in a group, alone, and a group that is fine beside them
+    for name, flags in (("uf", [4, 0]), ("ul", [0, 4]), ("ua", [4]), ("ok1", [0]), ("uf3", [4, 0, 0]), ("ul3", [0, 0, 4]), ("ok2", [0])):
+        recs += [rec(name, f | ((0x41 if i % 2 == 0 else 0x81) if paired else 0)) for i, f in enumerate(flags)]
+    recs += [rec("raw x"), rec("raw y"), rec("raw"), rec("raw")]  # raw names: no cut here
+    return recs
+
+
+@pytest.mark.parametrize("paired", [0, 1], ids=["se", "pe"])
+@pytest.mark.parametrize("budget", [None, 1, 7, 64])
+def test_unique_groups_of_every_size_across_batches(monkeypatch, paired, budget):
+    if budget:
+        monkeypatch.setenv("RSEM_ALNCHECK_BATCH_ITEMS", str(budget))
+    recs = unique_stream(paired)
+    keep, info = ar.device_keep(recs)
+    want = ar.unique_keep(recs)
+    assert keep.tolist() == want and 0 < sum(want) < len(recs)
+    n_groups = 1 + sum(a.name != b.name for a, b in zip(recs, recs[1:]))
+    assert info["n_groups"] == n_groups and info["n_kept"] == sum(want) and info["n_launches"] == 3 * info["n_batches"] and info["batch_items"] == (budget or ar.DEFAULT_BATCH_ITEMS)
+    assert info["n_batches"] == (1 if budget is None else (n_groups if budget == 1 else info["n_batches"])) and info["kernel_ms"] > 0
+
+
+def test_unique_many_small_groups():
+    rng = np.random.default_rng(5)
+    recs = []
+    for g in range(1500):
+        n = int(rng.integers(1, 4))
+        recs += [rec("read%d" % g, 4 if rng.random() < 0.1 else 0) for _ in range(n)]
+    keep, info = ar.device_keep(recs)
+    assert keep.tolist() == ar.unique_keep(recs) and info["n_groups"] == 1500 and info["n_batches"] == 1
