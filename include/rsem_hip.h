@@ -683,6 +683,61 @@ void rsem_alncheck_destroy(rsem_alncheck* h);
 int rsem_alncheck_unique(int device, int64_t n_records, const uint64_t* name_off /* n + 1 */, const uint8_t* names, const uint32_t* flag,
                          uint8_t* keep /* n_records */, rsem_alncheck_info* info /* may be NULL */);
 
+/* ---- mates made adjacent (rsem-scan-for-paired-end-reads) --------------------------------------------------------------------------
+ * rsem_pairscan_create touches no device.  rsem_pairscan_reorder replaces the loop of scanForPairedEndReads.cpp:78-126 with
+ * add_to_appropriate_arr (:24-32), get_pattern_code (:34-37) and less_than (:39-51) for records that are grouped by read name: record i
+ * has the name names[name_off[i] .. name_off[i + 1]) (no NUL) and its BAM fields flag, tid, pos, mpos.  A call takes whole runs of
+ * equal canonical names (the bytes before the first of " \t\n\r\f\v", sam_utils.h:45,54-61): no group crosses such a boundary.
+ * perm_out[k] is the index in this call of the k-th record the reference writes.
+ * Groups (:79-87, :117-122): a group opens at a record s, its name is the canonical name of s, its mode bit 0x1 of s's flag.  A
+ * single-end group runs on while the next record's RAW name equals that name and is written as it comes; a paired group runs on while
+ * the next record's CANONICAL name equals it.  On the device a record opens a group iff its canonical name differs from the record
+ * before (a hard start), or its raw name is longer than its canonical name and none of the hard start and the such records before it
+ * in its run has bit 0x1 -- a prefix count.
+ * A paired group (:83-115): its records are `both` (!(flag & 4) && (flag & 2)), partial_1 (else flag & 0x40), partial_2 (else flag &
+ * 0x80) or unknown.  First the `both` records sorted by less_than -- tid, min(pos, mpos), max(pos, mpos), then the pattern code (read 1: 0
+ * forward, 1 reverse; any other record: 1 forward, 0 reverse), all signed 32-bit -- STABLY: records that tie keep their order (the
+ * reference's std::sort leaves the order inside a tie to the library; up to 16 records it is an insertion sort and gives this
+ * order).  Then, each vector from its back: partial_1 and partial_2 in turns while both last, then what is left of one of them, each
+ * with the last unknown behind it, then the other unknown records.
+ * The verdict is the failing group of smallest index in the call, with the reference's first complaint about it: MIXED (a record
+ * without bit 0x1 in a paired group, :85), ODD_FULL (:89), ODD_PARTIAL (:90), and NO_PARTNER where the reference calls back() on an
+ * empty vector (:105,109: more left-over partial records than unknown ones).  With code != 0 perm_out is unspecified, and nothing
+ * runs behind the failing batch.
+ * The handle keeps its stream and its buffers between calls and grows them to the largest batch.  After a call with `last` it takes
+ * no more records (RSEM_ERR_STATE).
+ * Checked before a device is touched (RSEM_ERR_INVALID): a NULL handle, perm_out or verdict, negative counts, 2^32 records or more,
+ * name_off that does not start at 0 and ascend, a name of 0 or more than 254 bytes.
+ * The environment variable RSEM_PAIRSCAN_BATCH_ITEMS (a whole number >= 1, read at every call, anything else: RSEM_ERR_INVALID)
+ * replaces the batch budget of 2^22 records; a batch is whole runs of equal canonical names within the budget, a run above it is a
+ * batch of its own.  The results do not depend on it, n_batches does. */
+#define RSEM_PAIRSCAN_OK 0
+#define RSEM_PAIRSCAN_MIXED 1
+#define RSEM_PAIRSCAN_ODD_FULL 2
+#define RSEM_PAIRSCAN_ODD_PARTIAL 3
+#define RSEM_PAIRSCAN_NO_PARTNER 4
+typedef struct rsem_pairscan rsem_pairscan;
+typedef struct rsem_pairscan_verdict {
+    int32_t code;              /* 0 = nothing wrong, else RSEM_PAIRSCAN_* */
+    int32_t n_batches;
+    int64_t group;             /* the failing group's index among this call's groups; -1 if code == 0 */
+    int64_t group_record;      /* index in this call of its first record; -1 if code == 0 */
+    uint64_t n_records;        /* of this call */
+    uint64_t n_groups;         /* of this call; with code != 0: of the batches that ran */
+    uint64_t n_sorted_groups;  /* groups with two or more `both` records */
+    int32_t n_launches;        /* kernels and library calls: ten a batch, eleven where a group is sorted */
+    int32_t reserved;
+    uint64_t batch_items;      /* the budget in force */
+    uint64_t device_bytes;     /* held by the handle after the call */
+    double upload_ms;
+    double kernel_ms;          /* the batches' kernels and scans */
+} rsem_pairscan_verdict;
+int rsem_pairscan_create(rsem_pairscan** out, int device);
+int rsem_pairscan_reorder(rsem_pairscan* h, int64_t n_records, const uint64_t* name_off /* n + 1 */, const uint8_t* names, const uint32_t* flag,
+                          const int32_t* tid, const int32_t* pos, const int32_t* mpos, int32_t last, uint32_t* perm_out /* n_records */,
+                          rsem_pairscan_verdict* v);
+void rsem_pairscan_destroy(rsem_pairscan* h);
+
 #ifdef __cplusplus
 }
 #endif

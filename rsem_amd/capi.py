@@ -80,6 +80,12 @@ class AlncheckInfo(C.Structure):
                 ("batch_items", C.c_uint64), ("device_bytes", C.c_uint64), ("upload_ms", C.c_double), ("kernel_ms", C.c_double)]
 
 
+class PairscanVerdict(C.Structure):
+    _fields_ = [("code", C.c_int32), ("n_batches", C.c_int32), ("group", C.c_int64), ("group_record", C.c_int64), ("n_records", C.c_uint64), ("n_groups", C.c_uint64),
+                ("n_sorted_groups", C.c_uint64), ("n_launches", C.c_int32), ("reserved", C.c_int32), ("batch_items", C.c_uint64), ("device_bytes", C.c_uint64),
+                ("upload_ms", C.c_double), ("kernel_ms", C.c_double)]
+
+
 class EmProfile(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("estep_ms_sum", C.c_double), ("estep_launches", C.c_int32),
                 ("rounds", C.c_int32), ("algorithmic_bytes_per_round", C.c_uint64)]
@@ -166,6 +172,10 @@ def lib():
         L.rsem_alncheck_destroy.argtypes = [vp]
         L.rsem_alncheck_destroy.restype = None
         L.rsem_alncheck_unique.argtypes = [ci, C.c_int64, vp, vp, vp, vp, vp]
+        L.rsem_pairscan_create.argtypes = [C.POINTER(vp), ci]
+        L.rsem_pairscan_reorder.argtypes = [vp, C.c_int64] + [vp] * 6 + [i32, vp, vp]
+        L.rsem_pairscan_destroy.argtypes = [vp]
+        L.rsem_pairscan_destroy.restype = None
         _lib = L
     return _lib
 
@@ -742,3 +752,41 @@ def alncheck_unique(name_off, names, flag, device=0):
     info = AlncheckInfo()
     _check(lib().rsem_alncheck_unique(device, n, _ptr(name_off), _ptr(names), _ptr(flag), _ptr(keep), C.addressof(info)))
     return keep[:n], {f: getattr(info, f) for f, _ in AlncheckInfo._fields_}
+
+
+PAIRSCAN_OK, PAIRSCAN_MIXED, PAIRSCAN_ODD_FULL, PAIRSCAN_ODD_PARTIAL, PAIRSCAN_NO_PARTNER = range(5)
+
+
+class Pairscan:
+    """rsem_pairscan: the order in which rsem-scan-for-paired-end-reads writes the records of a name-grouped file.  The handle keeps
+    its device buffers between calls."""
+
+    def __init__(self, device=0):
+        self.h = C.c_void_p()
+        _check(lib().rsem_pairscan_create(C.byref(self.h), device))
+
+    def reorder(self, name_off, names, flag, tid, pos, mpos, last=False):
+        """rsem_pairscan_reorder over whole runs of equal canonical names.  Returns (perm, verdict as a dict): perm[k] is the input
+        index of the k-th output record (unspecified where verdict["code"] != 0)."""
+        name_off = np.ascontiguousarray(name_off, np.uint64)
+        names = np.frombuffer(names, np.uint8) if isinstance(names, (bytes, bytearray)) else np.ascontiguousarray(names, np.uint8)
+        flag = np.ascontiguousarray(flag, np.uint32)
+        tid, pos, mpos = (np.ascontiguousarray(x, np.int32) for x in (tid, pos, mpos))
+        n = len(flag)
+        assert len(name_off) == n + 1 and len(tid) == n and len(pos) == n and len(mpos) == n
+        perm = np.zeros(max(n, 1), np.uint32)
+        v = PairscanVerdict()
+        _check(lib().rsem_pairscan_reorder(self.h, n, _ptr(name_off), _ptr(names), _ptr(flag), _ptr(tid), _ptr(pos), _ptr(mpos), 1 if last else 0, _ptr(perm),
+                                           C.addressof(v)))
+        return perm[:n], {f: getattr(v, f) for f, _ in PairscanVerdict._fields_}
+
+    def close(self):
+        if self.h:
+            lib().rsem_pairscan_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
