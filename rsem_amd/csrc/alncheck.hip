@@ -20,29 +20,14 @@
 #include <vector>
 
 #include "alncheck_block.hpp"
-#include "common.hpp"
+#include "stage_util.hpp"
 
 using namespace rsem_alnk;
 
 namespace {
 
-struct Buf {  // a device buffer that only grows; keep: what it holds stays (the resident arrays)
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t bytes, size_t& total, size_t keep = 0) {
-        if (bytes <= cap) return hipSuccess;
-        const size_t want = bytes + bytes / 2 + 256;
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, want);
-        if (e != hipSuccess) return e;  // (what was there is still there)
-        if (p && keep) e = hipMemcpy(q, p, keep, hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) { (void)hipFree(q); return e; }
-        if (p) { (void)hipFree(p); total -= cap; }
-        p = q; cap = want; total += want;
-        return hipSuccess;
-    }
-    template <class T> T* as() const { return (T*)p; }
-};
+using rsem::blocks256;
+using Buf = rsem::GrowBuf<2>;  // a device buffer that only grows; keep: what it holds stays (the resident arrays)
 
 enum { B_NOFF, B_NAMES, B_FLAG, B_TID, B_POS, B_ISIZE, B_LQ, B_COFF, B_CIGAR, B_DETAIL, B_HASH, B_OPEN, B_SCAN, B_GHASH, B_GUNIT, B_SUNIT, B_UREF, B_RUNOFF, B_TMP,
        B_COUNT };
@@ -58,8 +43,7 @@ struct rsem_alncheck {
     Carry* d_carry[2] = {nullptr, nullptr};
     int carry_cur = 0;
     unsigned long long* d_verdict = nullptr;
-    hipStream_t st = nullptr;
-    hipEvent_t ea = nullptr, eb = nullptr, ec = nullptr;
+    rsem::StageQueue q;
     Buf buf[B_COUNT];
     Buf res_hash, res_ref, res_names;   // the closed and open groups of the file so far: 16 bytes a group and the names' bytes
     uint64_t n_groups = 0, names_used = 0;
@@ -101,24 +85,13 @@ __global__ void __launch_bounds__(256) k_unique_keep(int64_t n, const uint32_t* 
     if (i < n) keep[i] = unique_keep(incl, flag, n, i);
 }
 
-inline uint32_t blocks256(uint64_t n) { return (uint32_t)((n + 255) / 256); }
-
 // RSEM_ALNCHECK_BATCH_ITEMS and RSEM_ALNCHECK_HASH_BITS, read at every call
 int read_knobs(uint64_t& budget, int& hash_bits) {
     budget = kDefaultBatchItems;
-    hash_bits = 64;
-    if (const char* e = getenv("RSEM_ALNCHECK_BATCH_ITEMS")) {
-        char* end = nullptr;
-        const long long v = strtoll(e, &end, 10);
-        if (end == e || *end || v < 1) { rsem::set_last_error("RSEM_ALNCHECK_BATCH_ITEMS = '%s': a whole number from 1 on is expected", e); return RSEM_ERR_INVALID; }
-        budget = (uint64_t)v;
-    }
-    if (const char* e = getenv("RSEM_ALNCHECK_HASH_BITS")) {
-        char* end = nullptr;
-        const long long v = strtoll(e, &end, 10);
-        if (end == e || *end || v < 1 || v > 64) { rsem::set_last_error("RSEM_ALNCHECK_HASH_BITS = '%s': a whole number from 1 to 64 is expected", e); return RSEM_ERR_INVALID; }
-        hash_bits = (int)v;
-    }
+    uint64_t bits = 64;
+    if (int rc = rsem::env_whole("RSEM_ALNCHECK_BATCH_ITEMS", 1, LLONG_MAX, &budget)) return rc;
+    if (int rc = rsem::env_whole("RSEM_ALNCHECK_HASH_BITS", 1, 64, &bits)) return rc;
+    hash_bits = (int)bits;
     return RSEM_OK;
 }
 
@@ -141,10 +114,7 @@ int check_names(const char* who, int64_t n, const uint64_t* name_off, const uint
 int to_device(rsem_alncheck* h) {
     RSEM_HIP_TRY(hipSetDevice(h->device));
     if (h->on_device) return RSEM_OK;
-    RSEM_HIP_TRY(hipStreamCreate(&h->st));
-    RSEM_HIP_TRY(hipEventCreate(&h->ea));
-    RSEM_HIP_TRY(hipEventCreate(&h->eb));
-    RSEM_HIP_TRY(hipEventCreate(&h->ec));
+    RSEM_HIP_TRY(h->q.create());
     const size_t tb = std::max<size_t>(h->target_len.size() * 4, 8);
     RSEM_HIP_TRY(hipMalloc(&h->d_tlen, tb));
     h->device_bytes += tb;
@@ -177,9 +147,9 @@ int run_batch(rsem_alncheck* h, const PushCall& c, uint64_t lo, uint64_t nrec, i
     const uint64_t nu = (nrec + (uint64_t)mates - 1) / (uint64_t)mates, unit_base = lo / (uint64_t)mates;
     const uint64_t nb = c.name_off[lo + nrec] - c.name_off[lo], nw = c.cigar_off[lo + nrec] - c.cigar_off[lo];
     size_t t_scan = 0, t_sort = 0;
-    RSEM_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t_scan, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)(nu + 1), h->st));
+    RSEM_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t_scan, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)(nu + 1), h->q.st));
     RSEM_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, t_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)nu, 0,
-                                                    hash_bits, h->st));
+                                                    hash_bits, h->q.st));
     const size_t need[B_COUNT] = {(size_t)(nrec + 1) * 8, (size_t)nb, (size_t)nrec * 4, (size_t)nrec * 4, (size_t)nrec * 4, (size_t)nrec * 4, (size_t)nrec * 4, (size_t)(nrec + 1) * 8,
                                   (size_t)nw * 4, (size_t)nu * 4, (size_t)nu * 8, (size_t)(nu + 1) * 8, (size_t)(nu + 1) * 8, (size_t)nu * 8, (size_t)nu * 4, (size_t)nu * 4,
                                   (size_t)nu * 8, (h->run_off.size() + 1) * 8, std::max(t_scan, t_sort)};
@@ -197,8 +167,8 @@ int run_batch(rsem_alncheck* h, const PushCall& c, uint64_t lo, uint64_t nrec, i
     auto U64 = [&](int b) { return h->buf[b].as<uint64_t>(); };
     auto U32 = [&](int b) { return h->buf[b].as<uint32_t>(); };
     auto I32 = [&](int b) { return h->buf[b].as<int32_t>(); };
-    hipStream_t st = h->st;
-    RSEM_HIP_TRY(hipEventRecord(h->ea, st));
+    hipStream_t st = h->q.st;
+    RSEM_HIP_TRY(h->q.upload_begin());
     RSEM_HIP_TRY(hipMemcpyAsync(U64(B_NOFF), c.name_off + lo, (size_t)(nrec + 1) * 8, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemcpyAsync(h->buf[B_NAMES].p, c.names + c.name_off[lo], (size_t)nb, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemcpyAsync(U32(B_FLAG), c.flag + lo, (size_t)nrec * 4, hipMemcpyHostToDevice, st));
@@ -209,7 +179,7 @@ int run_batch(rsem_alncheck* h, const PushCall& c, uint64_t lo, uint64_t nrec, i
     RSEM_HIP_TRY(hipMemcpyAsync(U64(B_COFF), c.cigar_off + lo, (size_t)(nrec + 1) * 8, hipMemcpyHostToDevice, st));
     if (nw) RSEM_HIP_TRY(hipMemcpyAsync(U32(B_CIGAR), c.cigar + c.cigar_off[lo], (size_t)nw * 4, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemcpyAsync(U64(B_RUNOFF), h->run_off.data(), h->run_off.size() * 8, hipMemcpyHostToDevice, st));
-    RSEM_HIP_TRY(hipEventRecord(h->eb, st));
+    RSEM_HIP_TRY(h->q.upload_end());
 
     const Recs R{U64(B_NOFF), h->buf[B_NAMES].as<uint8_t>(), c.name_off[lo], U32(B_FLAG), I32(B_TID), I32(B_POS), I32(B_ISIZE), I32(B_LQ), U64(B_COFF), U32(B_CIGAR),
                  c.cigar_off[lo], (int64_t)nrec};
@@ -240,7 +210,7 @@ int run_batch(rsem_alncheck* h, const PushCall& c, uint64_t lo, uint64_t nrec, i
         hipLaunchKernelGGL(k_alncheck_lookup, dim3(blocks256(ng)), dim3(256), 0, st, ng, S, U32(B_SUNIT), U64(B_UREF), U32(B_DETAIL), unit_base, h->d_verdict);
         v->n_launches += 2;
     }
-    RSEM_HIP_TRY(hipEventRecord(h->ec, st));
+    RSEM_HIP_TRY(h->q.kernels_end());
     RSEM_HIP_TRY(hipMemcpyAsync(&word, h->d_verdict, 8, hipMemcpyDeviceToHost, st));
     RSEM_HIP_TRY(hipStreamSynchronize(st));
     RSEM_HIP_TRY(hipGetLastError());
@@ -255,12 +225,7 @@ int run_batch(rsem_alncheck* h, const PushCall& c, uint64_t lo, uint64_t nrec, i
         h->carry_cur ^= 1;
         opened += ng;
     }
-    float ms = 0;
-    RSEM_HIP_TRY(hipEventElapsedTime(&ms, h->ea, h->eb));
-    upload_ms += ms;
-    RSEM_HIP_TRY(hipEventElapsedTime(&ms, h->eb, h->ec));
-    kernel_ms += ms;
-    return RSEM_OK;
+    return h->q.add_laps(upload_ms, kernel_ms);
 }
 
 }  // namespace
@@ -282,14 +247,11 @@ extern "C" void rsem_alncheck_destroy(rsem_alncheck* h) {
     if (!h) return;
     if (h->on_device) {
         (void)hipSetDevice(h->device);
-        for (void* p : {h->d_tlen, (void*)h->d_carry[0], (void*)h->d_carry[1], (void*)h->d_verdict, h->res_hash.p, h->res_ref.p, h->res_names.p})
+        for (void* p : {h->d_tlen, (void*)h->d_carry[0], (void*)h->d_carry[1], (void*)h->d_verdict})
             if (p) (void)hipFree(p);
-        for (Buf& b : h->buf)
-            if (b.p) (void)hipFree(b.p);
-        if (h->ea) (void)hipEventDestroy(h->ea);
-        if (h->eb) (void)hipEventDestroy(h->eb);
-        if (h->ec) (void)hipEventDestroy(h->ec);
-        if (h->st) (void)hipStreamDestroy(h->st);
+        for (Buf* b : {&h->res_hash, &h->res_ref, &h->res_names}) b->release(h->device_bytes);
+        for (Buf& b : h->buf) b.release(h->device_bytes);
+        h->q.release();
     }
     delete h;
 }
@@ -400,68 +362,54 @@ extern "C" int rsem_alncheck_unique(int device, int64_t n_records, const uint64_
         lo = hi;
     }
     RSEM_HIP_TRY(hipSetDevice(device));
-    hipStream_t st = nullptr;
-    hipEvent_t ea = nullptr, eb = nullptr, ec = nullptr;
-    void *d_noff = nullptr, *d_names = nullptr, *d_flag = nullptr, *d_start = nullptr, *d_incl = nullptr, *d_keep = nullptr, *d_tmp = nullptr;
+    rsem::StageQueue q;
+    RSEM_HIP_TRY(q.create());
+    hipStream_t st = q.st;
     size_t t_scan = 0;
-    auto run = [&]() -> int {
-        RSEM_HIP_TRY(hipStreamCreate(&st));
-        RSEM_HIP_TRY(hipEventCreate(&ea));
-        RSEM_HIP_TRY(hipEventCreate(&eb));
-        RSEM_HIP_TRY(hipEventCreate(&ec));
-        RSEM_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, t_scan, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)largest, st));
-        RSEM_HIP_TRY(hipMalloc(&d_noff, (size_t)(largest + 1) * 8));
-        RSEM_HIP_TRY(hipMalloc(&d_names, (size_t)largest_bytes + 8));
-        RSEM_HIP_TRY(hipMalloc(&d_flag, (size_t)largest * 4));
-        RSEM_HIP_TRY(hipMalloc(&d_start, (size_t)largest * 4));
-        RSEM_HIP_TRY(hipMalloc(&d_incl, (size_t)largest * 4));
-        RSEM_HIP_TRY(hipMalloc(&d_keep, (size_t)largest + 8));
-        RSEM_HIP_TRY(hipMalloc(&d_tmp, t_scan + 8));
-        double upload_ms = 0, kernel_ms = 0;
-        uint64_t n_groups = 0, n_kept = 0;
-        for (const auto& b : batches) {
-            const uint64_t lo = b.first, n = b.second - b.first, nb = name_off[b.second] - name_off[lo];
-            RSEM_HIP_TRY(hipEventRecord(ea, st));
-            RSEM_HIP_TRY(hipMemcpyAsync(d_noff, name_off + lo, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-            RSEM_HIP_TRY(hipMemcpyAsync(d_names, names + name_off[lo], (size_t)nb, hipMemcpyHostToDevice, st));
-            RSEM_HIP_TRY(hipMemcpyAsync(d_flag, flag + lo, (size_t)n * 4, hipMemcpyHostToDevice, st));
-            RSEM_HIP_TRY(hipEventRecord(eb, st));
-            const Recs R{(const uint64_t*)d_noff, (const uint8_t*)d_names, name_off[lo], (const uint32_t*)d_flag, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, (int64_t)n};
-            hipLaunchKernelGGL(k_unique_start, dim3(blocks256(n)), dim3(256), 0, st, R, (uint32_t*)d_start);
-            size_t tb = t_scan + 8;
-            RSEM_HIP_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp, tb, (const uint32_t*)d_start, (uint32_t*)d_incl, (int)n, st));
-            hipLaunchKernelGGL(k_unique_keep, dim3(blocks256(n)), dim3(256), 0, st, (int64_t)n, (const uint32_t*)d_incl, (const uint32_t*)d_flag, (uint8_t*)d_keep);
-            RSEM_HIP_TRY(hipEventRecord(ec, st));
-            uint32_t groups = 0;
-            RSEM_HIP_TRY(hipMemcpyAsync(keep + lo, d_keep, (size_t)n, hipMemcpyDeviceToHost, st));
-            RSEM_HIP_TRY(hipMemcpyAsync(&groups, (const uint32_t*)d_incl + (n - 1), 4, hipMemcpyDeviceToHost, st));
-            RSEM_HIP_TRY(hipStreamSynchronize(st));
-            RSEM_HIP_TRY(hipGetLastError());
-            float ms = 0;
-            RSEM_HIP_TRY(hipEventElapsedTime(&ms, ea, eb));
-            upload_ms += ms;
-            RSEM_HIP_TRY(hipEventElapsedTime(&ms, eb, ec));
-            kernel_ms += ms;
-            n_groups += groups;
-            for (uint64_t i = lo; i < b.second; i++) n_kept += keep[i];
-        }
-        if (info) {
-            info->n_groups = n_groups;
-            info->n_kept = n_kept;
-            info->n_batches = (int32_t)batches.size();
-            info->n_launches = 3 * (int32_t)batches.size();
-            info->device_bytes = (size_t)(largest + 1) * 8 + (size_t)largest_bytes + 8 + (size_t)largest * 12 + (size_t)largest + 8 + t_scan + 8;
-            info->upload_ms = upload_ms;
-            info->kernel_ms = kernel_ms;
-        }
-        return RSEM_OK;
-    };
-    const int rc = run();
-    for (void* p : {d_noff, d_names, d_flag, d_start, d_incl, d_keep, d_tmp})
-        if (p) (void)hipFree(p);
-    if (ea) (void)hipEventDestroy(ea);
-    if (eb) (void)hipEventDestroy(eb);
-    if (ec) (void)hipEventDestroy(ec);
-    if (st) (void)hipStreamDestroy(st);
-    return rc;
+    RSEM_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, t_scan, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)largest, st));
+    rsem::DevMem mem;
+    uint64_t* d_noff = nullptr;
+    uint8_t *d_names = nullptr, *d_keep = nullptr, *d_tmp = nullptr;
+    uint32_t *d_flag = nullptr, *d_start = nullptr, *d_incl = nullptr;
+    RSEM_HIP_TRY(mem.alloc(&d_noff, (size_t)largest + 1));
+    RSEM_HIP_TRY(mem.alloc(&d_names, (size_t)largest_bytes + 8));
+    RSEM_HIP_TRY(mem.alloc(&d_flag, (size_t)largest));
+    RSEM_HIP_TRY(mem.alloc(&d_start, (size_t)largest));
+    RSEM_HIP_TRY(mem.alloc(&d_incl, (size_t)largest));
+    RSEM_HIP_TRY(mem.alloc(&d_keep, (size_t)largest + 8));
+    RSEM_HIP_TRY(mem.alloc(&d_tmp, t_scan + 8));
+    double upload_ms = 0, kernel_ms = 0;
+    uint64_t n_groups = 0, n_kept = 0;
+    for (const auto& b : batches) {
+        const uint64_t lo = b.first, n = b.second - b.first, nb = name_off[b.second] - name_off[lo];
+        RSEM_HIP_TRY(q.upload_begin());
+        RSEM_HIP_TRY(hipMemcpyAsync(d_noff, name_off + lo, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+        RSEM_HIP_TRY(hipMemcpyAsync(d_names, names + name_off[lo], (size_t)nb, hipMemcpyHostToDevice, st));
+        RSEM_HIP_TRY(hipMemcpyAsync(d_flag, flag + lo, (size_t)n * 4, hipMemcpyHostToDevice, st));
+        RSEM_HIP_TRY(q.upload_end());
+        const Recs R{d_noff, d_names, name_off[lo], d_flag, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, (int64_t)n};
+        hipLaunchKernelGGL(k_unique_start, dim3(blocks256(n)), dim3(256), 0, st, R, d_start);
+        size_t tb = t_scan + 8;
+        RSEM_HIP_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp, tb, (const uint32_t*)d_start, d_incl, (int)n, st));
+        hipLaunchKernelGGL(k_unique_keep, dim3(blocks256(n)), dim3(256), 0, st, (int64_t)n, (const uint32_t*)d_incl, (const uint32_t*)d_flag, d_keep);
+        RSEM_HIP_TRY(q.kernels_end());
+        uint32_t groups = 0;
+        RSEM_HIP_TRY(hipMemcpyAsync(keep + lo, d_keep, (size_t)n, hipMemcpyDeviceToHost, st));
+        RSEM_HIP_TRY(hipMemcpyAsync(&groups, d_incl + (n - 1), 4, hipMemcpyDeviceToHost, st));
+        RSEM_HIP_TRY(hipStreamSynchronize(st));
+        RSEM_HIP_TRY(hipGetLastError());
+        if (int rc = q.add_laps(upload_ms, kernel_ms)) return rc;
+        n_groups += groups;
+        for (uint64_t i = lo; i < b.second; i++) n_kept += keep[i];
+    }
+    if (info) {
+        info->n_groups = n_groups;
+        info->n_kept = n_kept;
+        info->n_batches = (int32_t)batches.size();
+        info->n_launches = 3 * (int32_t)batches.size();
+        info->device_bytes = mem.bytes;
+        info->upload_ms = upload_ms;
+        info->kernel_ms = kernel_ms;
+    }
+    return RSEM_OK;
 }

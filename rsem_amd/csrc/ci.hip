@@ -24,37 +24,19 @@
 #include <cstdlib>
 #include <vector>
 
-#include "common.hpp"
 #include "rng.hpp"
+#include "stage_util.hpp"
 
 namespace {
 
 using rsem::kEpsilon;
+using rsem::DevMem;
+using rsem::EventGuard;
 using rsem::Philox;
+using rsem::StreamGuard;
 
 constexpr int kBlock = 256;
 constexpr uint32_t kDrawTag = 0x43495331u;  // 'CIS1'
-
-struct DevMem {  // frees what it owns on scope exit
-    std::vector<void*> ptrs;
-    ~DevMem() { for (void* p : ptrs) (void)hipFree(p); }
-    template <class T> hipError_t alloc(T** p, size_t n) {
-        hipError_t e = hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-};
-
-struct EventGuard {  // events / streams released on every exit path
-    hipEvent_t e = nullptr;
-    ~EventGuard() { if (e) (void)hipEventDestroy(e); }
-    hipError_t create() { return hipEventCreate(&e); }
-};
-struct StreamGuard {
-    hipStream_t s = nullptr;
-    ~StreamGuard() { if (s) (void)hipStreamDestroy(s); }
-    hipError_t create() { return hipStreamCreate(&s); }
-};
 
 // y[j][s] for transcripts j in this block's chunk, samples s = lane
 __global__ void __launch_bounds__(64) k_ci_draw(int32_t M, int32_t nS, int32_t nSpC, int32_t chunk, const int32_t* __restrict__ cvecs,

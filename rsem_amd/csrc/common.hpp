@@ -18,6 +18,7 @@ constexpr double kEpsilon = 1e-300;  // utils.h:19
 constexpr int kWave = 64;            // gfx950 wavefront
 
 inline int ceil_div(uint64_t a, uint64_t b) { return (int)((a + b - 1) / b); }
+inline uint32_t blocks256(uint64_t n) { return (uint32_t)((n + 255) / 256); }  // workgroups of 256 lanes, a lane an item
 
 // one empty launch per translation unit = its code object is loaded (rsem_hip_preload, status.hip); defined in em.hip, model.hip,
 // gibbs.hip, ci.hip

@@ -17,34 +17,13 @@
 #include <cstdlib>
 #include <vector>
 
-#include "common.hpp"
 #include "depth_block.hpp"
+#include "stage_util.hpp"
 
 namespace {
 
 using namespace rsem_depth;
-
-struct DevMem {  // frees what it owns on scope exit
-    std::vector<void*> ptrs;
-    size_t bytes = 0;
-    ~DevMem() { for (void* p : ptrs) (void)hipFree(p); }
-    template <class T> hipError_t alloc(T** p, size_t n) {
-        const size_t b = std::max<size_t>(n, 1) * sizeof(T);
-        hipError_t e = hipMalloc((void**)p, b);
-        if (e == hipSuccess) { ptrs.push_back(*p); bytes += b; }
-        return e;
-    }
-};
-struct EventGuard {
-    hipEvent_t e = nullptr;
-    ~EventGuard() { if (e) (void)hipEventDestroy(e); }
-    hipError_t create() { return hipEventCreate(&e); }
-};
-struct StreamGuard {
-    hipStream_t s = nullptr;
-    ~StreamGuard() { if (s) (void)hipStreamDestroy(s); }
-    hipError_t create() { return hipStreamCreate(&s); }
-};
+using rsem::blocks256;
 
 // cnt has n + 1 elements: the scan's last output is the number of entries
 __global__ void __launch_bounds__(256) k_count(const uint64_t* __restrict__ start, const uint32_t* __restrict__ len, uint32_t n, uint32_t* __restrict__ cnt) {
@@ -74,8 +53,6 @@ __global__ void __launch_bounds__(kTileThreads) k_accumulate(const uint32_t* __r
     accumulate_tile(tiles[blockIdx.x], e0, seg_off[blockIdx.x + 1] - e0, blk_of, start, len, w, depth, n_bases, stage);
 }
 
-inline uint32_t blocks256(uint64_t n) { return (uint32_t)((n + 255) / 256); }
-
 struct Batch { uint64_t lo, hi, entries; };
 
 int run(int device, uint64_t n_bases, const std::vector<Batch>& batches, uint64_t max_blocks, uint64_t max_entries, const uint64_t* start,
@@ -84,11 +61,9 @@ int run(int device, uint64_t n_bases, const std::vector<Batch>& batches, uint64_
     const int bits = tile_bits(n_tiles);
 
     RSEM_HIP_TRY(hipSetDevice(device));
-    StreamGuard sg;
-    RSEM_HIP_TRY(sg.create());
-    hipStream_t st = sg.s;
-    EventGuard ea, eb, ec;
-    RSEM_HIP_TRY(ea.create()); RSEM_HIP_TRY(eb.create()); RSEM_HIP_TRY(ec.create());
+    rsem::StageQueue q;
+    RSEM_HIP_TRY(q.create());
+    hipStream_t st = q.st;
 
     // the library's temporary storage for the largest batch
     size_t tmp_bytes = 0;
@@ -110,7 +85,7 @@ int run(int device, uint64_t n_bases, const std::vector<Batch>& batches, uint64_
                              "%zu are free", (unsigned long long)n_bases, (unsigned long long)max_blocks, (unsigned long long)max_entries, need, free_b);
         return RSEM_ERR_NOMEM;
     }
-    DevMem mem;
+    rsem::DevMem mem;
     double *d_depth = nullptr, *d_w = nullptr;
     uint64_t* d_start = nullptr;
     uint32_t *d_len = nullptr, *d_cnt = nullptr, *d_off = nullptr, *d_keys[2] = {nullptr, nullptr}, *d_vals[2] = {nullptr, nullptr};
@@ -133,28 +108,22 @@ int run(int device, uint64_t n_bases, const std::vector<Batch>& batches, uint64_
     RSEM_HIP_TRY(mem.alloc(&d_tmp, tmp_bytes));
 
     double upload_ms = 0, kernel_ms = 0;
-    auto lap = [&](hipEvent_t a, hipEvent_t b, double& into) -> int {
-        float ms = 0;
-        RSEM_HIP_TRY(hipEventElapsedTime(&ms, a, b));
-        into += ms;
-        return RSEM_OK;
-    };
-    RSEM_HIP_TRY(hipEventRecord(ea.e, st));
+    RSEM_HIP_TRY(q.upload_begin());
     RSEM_HIP_TRY(hipMemcpyAsync(d_depth, depth, (size_t)n_bases * 8, hipMemcpyHostToDevice, st));
-    RSEM_HIP_TRY(hipEventRecord(eb.e, st));
+    RSEM_HIP_TRY(q.upload_end());
     RSEM_HIP_TRY(hipStreamSynchronize(st));
-    if (int rc = lap(ea.e, eb.e, upload_ms)) return rc;
+    if (int rc = q.add_upload_lap(upload_ms)) return rc;
 
     uint64_t n_entries = 0, n_touched = 0;
     int32_t n_launches = 0;
     for (const Batch& b : batches) {
         if (!b.entries) continue;  // blocks without a base
         const uint32_t n = (uint32_t)(b.hi - b.lo), ne = (uint32_t)b.entries;
-        RSEM_HIP_TRY(hipEventRecord(ea.e, st));
+        RSEM_HIP_TRY(q.upload_begin());
         RSEM_HIP_TRY(hipMemcpyAsync(d_start, start + b.lo, (size_t)n * 8, hipMemcpyHostToDevice, st));
         RSEM_HIP_TRY(hipMemcpyAsync(d_len, len + b.lo, (size_t)n * 4, hipMemcpyHostToDevice, st));
         RSEM_HIP_TRY(hipMemcpyAsync(d_w, w + b.lo, (size_t)n * 8, hipMemcpyHostToDevice, st));
-        RSEM_HIP_TRY(hipEventRecord(eb.e, st));
+        RSEM_HIP_TRY(q.upload_end());
         hipLaunchKernelGGL(k_count, dim3(blocks256((uint64_t)n + 1)), dim3(256), 0, st, d_start, d_len, n, d_cnt);
         size_t tb = tmp_bytes;
         RSEM_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_cnt, d_off, (int)(n + 1), st));
@@ -185,11 +154,10 @@ int run(int device, uint64_t n_bases, const std::vector<Batch>& batches, uint64_
         tb = tmp_bytes;
         RSEM_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_runs, d_seg, (int)(nruns + 1), st));  // (its last output does not read d_runs[nruns])
         hipLaunchKernelGGL(k_accumulate, dim3(nruns), dim3(kTileThreads), 0, st, d_tiles, d_seg, bv.Current(), d_start, d_len, d_w, d_depth, n_bases);
-        RSEM_HIP_TRY(hipEventRecord(ec.e, st));
+        RSEM_HIP_TRY(q.kernels_end());
         RSEM_HIP_TRY(hipStreamSynchronize(st));
         RSEM_HIP_TRY(hipGetLastError());
-        if (int rc = lap(ea.e, eb.e, upload_ms)) return rc;
-        if (int rc = lap(eb.e, ec.e, kernel_ms)) return rc;
+        if (int rc = q.add_laps(upload_ms, kernel_ms)) return rc;
         n_entries += ne;
         n_touched += nruns;
         n_launches += 7;
@@ -224,15 +192,7 @@ extern "C" int rsem_depth_accumulate(int device, uint64_t n_bases, uint64_t n_bl
         }
     }
     uint64_t budget = kDefaultBatchItems;
-    if (const char* e = getenv("RSEM_DEPTH_BATCH_ITEMS")) {  // a test and measurement knob, read at call time
-        char* end = nullptr;
-        const long long v = strtoll(e, &end, 10);
-        if (end == e || *end || v < 1) {
-            rsem::set_last_error("RSEM_DEPTH_BATCH_ITEMS = '%s': a whole number from 1 on is expected", e);
-            return RSEM_ERR_INVALID;
-        }
-        budget = (uint64_t)v;
-    }
+    if (int rc = rsem::env_whole("RSEM_DEPTH_BATCH_ITEMS", 1, LLONG_MAX, &budget)) return rc;  // a test and measurement knob, read at call time
     if (info) {
         memset(info, 0, sizeof(*info));
         info->batch_items = budget;

@@ -20,9 +20,9 @@
 #include <cstdlib>
 #include <vector>
 
-#include "common.hpp"
 #include "simt_macros.hpp"
 #include "gibbs_diag_math.hpp"
+#include "stage_util.hpp"
 
 namespace {
 
@@ -33,26 +33,6 @@ constexpr int kTileRows = 128;       // samples it holds in LDS at a time (64 Ki
 constexpr int kDefaultL0 = 15;
 constexpr int kMaxL0 = 63;
 constexpr size_t kLongLdsBytes = 32 << 10;  // series of one transcript that k_diag_long keeps in LDS (five of its one-wave workgroups per CU)
-
-struct DevMem {  // frees what it owns on scope exit
-    std::vector<void*> ptrs;
-    ~DevMem() { for (void* p : ptrs) (void)hipFree(p); }
-    template <class T> hipError_t alloc(T** p, size_t n) {
-        hipError_t e = hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-};
-struct EventGuard {
-    hipEvent_t e = nullptr;
-    ~EventGuard() { if (e) (void)hipEventDestroy(e); }
-    hipError_t create() { return hipEventCreate(&e); }
-};
-struct StreamGuard {
-    hipStream_t s = nullptr;
-    ~StreamGuard() { if (s) (void)hipStreamDestroy(s); }
-    hipError_t create() { return hipStreamCreate(&s); }
-};
 
 // The sums of all sequences: field f of sequence j for column c at part[((j * F) + f) * Mp + c], F = 2 + 2 Lc:
 // f = 0: s1, 1: s2, 2 .. Lc+1: c_1 .. c_Lc, Lc+2 .. 2Lc+1: e_1 .. e_Lc.
@@ -279,12 +259,10 @@ extern "C" int rsem_gibbs_diagnose(int device, int32_t M, int nchains, const int
                              "%zu of sums), %zu are free", m, n, M + 1, need, data_ints * 4, part_words * 8, free_b);
         return RSEM_ERR_NOMEM;
     }
-    StreamGuard sg;
-    RSEM_HIP_TRY(sg.create());
-    hipStream_t st = sg.s;
-    EventGuard e0, e1, e2;
-    RSEM_HIP_TRY(e0.create()); RSEM_HIP_TRY(e1.create()); RSEM_HIP_TRY(e2.create());
-    DevMem mem;
+    rsem::StageQueue q;
+    RSEM_HIP_TRY(q.create());
+    hipStream_t st = q.st;
+    rsem::DevMem mem;
     int32_t *d_data = nullptr, *d_lag = nullptr, *d_list = nullptr, *d_count = nullptr;
     int64_t* d_part = nullptr;
     double *d_mean = nullptr, *d_sd = nullptr, *d_rhat = nullptr, *d_ess = nullptr;
@@ -298,7 +276,7 @@ extern "C" int rsem_gibbs_diagnose(int device, int32_t M, int nchains, const int
     L.data = d_data; L.part = d_part;
 
     // upload: the last n' rows of every chain, each row at a pitch of Mp ints (a multiple of 16 bytes; the columns behind M are zero)
-    RSEM_HIP_TRY(hipEventRecord(e0.e, st));
+    RSEM_HIP_TRY(q.upload_begin());
     RSEM_HIP_TRY(hipMemsetAsync(d_data, 0, data_ints * 4, st));
     RSEM_HIP_TRY(hipMemsetAsync(d_count, 0, 2 * sizeof(int32_t), st));
     for (int k = 0; k < nchains; k++) {
@@ -306,7 +284,7 @@ extern "C" int rsem_gibbs_diagnose(int device, int32_t M, int nchains, const int
         RSEM_HIP_TRY(hipMemcpy2DAsync(d_data + (size_t)k * nused * L.Mp, (size_t)L.Mp * 4, src, ((size_t)M + 1) * 4, ((size_t)M + 1) * 4, (size_t)nused,
                                       hipMemcpyHostToDevice, st));
     }
-    RSEM_HIP_TRY(hipEventRecord(e1.e, st));
+    RSEM_HIP_TRY(q.upload_end());
 
     const int rows_lds = std::min(n, kTileRows);
     hipLaunchKernelGGL(k_diag_short, dim3((unsigned)(L.Mp / kTileCols), (unsigned)m), dim3(kTileCols), (size_t)rows_lds * kTileCols * 4, st, L, rows_lds);
@@ -327,7 +305,7 @@ extern "C" int rsem_gibbs_diagnose(int device, int32_t M, int nchains, const int
     const int sum_blocks = std::min(kSummaryBlocks, rsem::ceil_div((uint64_t)M, 256));
     hipLaunchKernelGGL(k_diag_summary, dim3(sum_blocks), dim3(256), 0, st, M, d_rhat, d_ess, d_best + 1);
     hipLaunchKernelGGL(k_diag_summary_parts, dim3(1), dim3(256), 0, st, sum_blocks, d_best + 1, d_best);
-    RSEM_HIP_TRY(hipEventRecord(e2.e, st));
+    RSEM_HIP_TRY(q.kernels_end());
     Best best;
     RSEM_HIP_TRY(hipMemcpyAsync(&best, d_best, sizeof(Best), hipMemcpyDeviceToHost, st));
     const size_t M1 = (size_t)M + 1;
@@ -339,9 +317,8 @@ extern "C" int rsem_gibbs_diagnose(int device, int32_t M, int nchains, const int
     RSEM_HIP_TRY(hipStreamSynchronize(st));
     RSEM_HIP_TRY(hipGetLastError());
     if (summary) {
-        float up = 0, kern = 0;
-        RSEM_HIP_TRY(hipEventElapsedTime(&up, e0.e, e1.e));
-        RSEM_HIP_TRY(hipEventElapsedTime(&kern, e1.e, e2.e));
+        double up = 0, kern = 0;
+        if (int rc = q.add_laps(up, kern)) return rc;
         summary->n_used = nused; summary->sequences = m; summary->n_defined = best.n_defined;
         summary->max_rhat_id = best.max_id; summary->min_ess_id = best.min_id;
         summary->n_rhat_gt_1p01 = best.n_1p01; summary->n_rhat_gt_1p1 = best.n_1p1; summary->n_long = n_long - counts[1];

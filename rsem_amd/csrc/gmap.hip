@@ -19,26 +19,15 @@
 #include <mutex>
 #include <vector>
 
-#include "common.hpp"
 #include "gmap_block.hpp"
+#include "stage_util.hpp"
 
 using namespace rsem_gmapk;
 
 namespace {
 
-struct Buf {  // a device buffer that only grows
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t bytes, size_t& total) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) { (void)hipFree(p); total -= cap; p = nullptr; cap = 0; }
-        const size_t want = bytes + bytes / 4 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) { cap = want; total += want; }
-        return e;
-    }
-    template <class T> T* as() const { return (T*)p; }
-};
+using rsem::blocks256;
+using Buf = rsem::GrowBuf<4>;  // a device buffer that only grows
 
 enum { B_TR, B_POS, B_LQ, B_FLAG, B_W, B_GOFF, B_SMALL, B_LARGE, B_OTID, B_OPOS, B_OFLAG, B_NCIG, B_BIN, B_HASN, B_COFF, B_CIGAR, B_ORDER, B_HEAD,
        B_WSUM, B_SCAN, B_OSRC, B_OW, B_TMP, B_COUNT };
@@ -54,8 +43,7 @@ struct rsem_gmap {
     std::vector<uint64_t> exon_off;
     bool on_device = false;
     void *d_minus = nullptr, *d_length = nullptr, *d_out_tid = nullptr, *d_exon_off = nullptr, *d_start = nullptr, *d_end = nullptr, *d_cum = nullptr;
-    hipStream_t st = nullptr;
-    hipEvent_t ea = nullptr, eb = nullptr, ec = nullptr;
+    rsem::StageQueue q;
     Buf buf[B_COUNT];
     size_t device_bytes = 0;
     std::mutex mu;  // one call at a time on a handle
@@ -112,15 +100,10 @@ __global__ void __launch_bounds__(256) k_gmap_emit(uint32_t n, const uint32_t* _
     ow[o] = wsum[p];
 }
 
-inline uint32_t blocks256(uint64_t n) { return (uint32_t)((n + 255) / 256); }
-
 int to_device(rsem_gmap* h) {
     RSEM_HIP_TRY(hipSetDevice(h->device));
     if (h->on_device) return RSEM_OK;
-    RSEM_HIP_TRY(hipStreamCreate(&h->st));
-    RSEM_HIP_TRY(hipEventCreate(&h->ea));
-    RSEM_HIP_TRY(hipEventCreate(&h->eb));
-    RSEM_HIP_TRY(hipEventCreate(&h->ec));
+    RSEM_HIP_TRY(h->q.create());
     auto up = [&](void** d, const void* src, size_t bytes) -> hipError_t {
         hipError_t e = hipMalloc(d, std::max<size_t>(bytes, 8));
         if (e != hipSuccess) return e;
@@ -172,8 +155,8 @@ int run_batch(rsem_gmap* h, const Call& c, uint64_t glo, uint64_t ghi, uint64_t&
     const uint32_t n_small = (uint32_t)small.size(), nb_small = (n_small + 3) / 4, n_large = (uint32_t)large.size();
 
     size_t t_scan_m = 0, t_scan_a = 0;
-    RSEM_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t_scan_m, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)(nm + 1), h->st));
-    RSEM_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t_scan_a, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)(na + 1), h->st));
+    RSEM_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t_scan_m, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)(nm + 1), h->q.st));
+    RSEM_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t_scan_a, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)(na + 1), h->q.st));
     const size_t tmp_bytes = std::max(t_scan_m, t_scan_a);
     const size_t need[B_COUNT] = {(size_t)nm * 4, (size_t)nm * 4, (size_t)nm * 4, (size_t)nm * 4, (size_t)na * 4, ((size_t)ng + 1) * 4, (size_t)ng * 4, (size_t)ng * 4,
                                   (size_t)nm * 4, (size_t)nm * 4, (size_t)nm * 4, ((size_t)nm + 1) * 4, (size_t)nm * 4, (size_t)nm * 4, ((size_t)nm + 1) * 4,
@@ -182,11 +165,11 @@ int run_batch(rsem_gmap* h, const Call& c, uint64_t glo, uint64_t ghi, uint64_t&
     auto I32 = [&](int b) { return h->buf[b].as<int32_t>(); };
     auto U32 = [&](int b) { return h->buf[b].as<uint32_t>(); };
     auto F32 = [&](int b) { return h->buf[b].as<float>(); };
-    hipStream_t st = h->st;
+    hipStream_t st = h->q.st;
     const Ref R{(const uint8_t*)h->d_minus, (const int32_t*)h->d_length, (const int32_t*)h->d_out_tid, (const uint64_t*)h->d_exon_off,
                 (const int32_t*)h->d_start, (const int32_t*)h->d_end, (const int32_t*)h->d_cum};
 
-    RSEM_HIP_TRY(hipEventRecord(h->ea, st));
+    RSEM_HIP_TRY(h->q.upload_begin());
     RSEM_HIP_TRY(hipMemcpyAsync(I32(B_TR), c.tr + m_lo, (size_t)nm * 4, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemcpyAsync(I32(B_POS), c.pos + m_lo, (size_t)nm * 4, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemcpyAsync(I32(B_LQ), c.l_qseq + m_lo, (size_t)nm * 4, hipMemcpyHostToDevice, st));
@@ -196,7 +179,7 @@ int run_batch(rsem_gmap* h, const Call& c, uint64_t glo, uint64_t ghi, uint64_t&
     if (n_small) RSEM_HIP_TRY(hipMemcpyAsync(U32(B_SMALL), small.data(), (size_t)n_small * 4, hipMemcpyHostToDevice, st));
     if (n_large) RSEM_HIP_TRY(hipMemcpyAsync(U32(B_LARGE), large.data(), (size_t)n_large * 4, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemsetAsync(U32(B_HEAD) + na, 0, 4, st));
-    RSEM_HIP_TRY(hipEventRecord(h->eb, st));
+    RSEM_HIP_TRY(h->q.upload_end());
 
     hipLaunchKernelGGL(k_gmap_count, dim3(blocks256((uint64_t)nm + 1)), dim3(256), 0, st, R, nm, I32(B_TR), I32(B_POS), I32(B_LQ), U32(B_FLAG), I32(B_OTID),
                        I32(B_OPOS), U32(B_OFLAG), U32(B_NCIG), U32(B_BIN), U32(B_HASN));
@@ -222,7 +205,7 @@ int run_batch(rsem_gmap* h, const Call& c, uint64_t glo, uint64_t ghi, uint64_t&
     tb = h->buf[B_TMP].cap;
     RSEM_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(h->buf[B_TMP].p, tb, U32(B_HEAD), U32(B_SCAN), (int)(na + 1), st));
     hipLaunchKernelGGL(k_gmap_emit, dim3(blocks256(na)), dim3(256), 0, st, na, U32(B_ORDER), U32(B_HEAD), F32(B_WSUM), U32(B_SCAN), U32(B_OSRC), F32(B_OW));
-    RSEM_HIP_TRY(hipEventRecord(h->ec, st));
+    RSEM_HIP_TRY(h->q.kernels_end());
 
     uint32_t n_out = 0;
     std::vector<uint32_t> coff(nm + 1), osrc(na);
@@ -245,11 +228,7 @@ int run_batch(rsem_gmap* h, const Call& c, uint64_t glo, uint64_t ghi, uint64_t&
     }
     for (uint32_t i = 0; i <= nm; i++) c.cigar_off[m_lo + i] = words_done + coff[i];
     for (uint32_t k = 0; k < n_out; k++) c.out_src[out_done + k] = a_lo + osrc[k];
-    float ms = 0;
-    RSEM_HIP_TRY(hipEventElapsedTime(&ms, h->ea, h->eb));
-    upload_ms += ms;
-    RSEM_HIP_TRY(hipEventElapsedTime(&ms, h->eb, h->ec));
-    kernel_ms += ms;
+    if (int rc = h->q.add_laps(upload_ms, kernel_ms)) return rc;
     words_done += words;
     out_done += n_out;
     if (info) info->n_launches += 6;
@@ -312,12 +291,8 @@ extern "C" void rsem_gmap_destroy(rsem_gmap* h) {
         (void)hipSetDevice(h->device);
         for (void* p : {h->d_minus, h->d_length, h->d_out_tid, h->d_exon_off, h->d_start, h->d_end, h->d_cum})
             if (p) (void)hipFree(p);
-        for (Buf& b : h->buf)
-            if (b.p) (void)hipFree(b.p);
-        if (h->ea) (void)hipEventDestroy(h->ea);
-        if (h->eb) (void)hipEventDestroy(h->eb);
-        if (h->ec) (void)hipEventDestroy(h->ec);
-        if (h->st) (void)hipStreamDestroy(h->st);
+        for (Buf& b : h->buf) b.release(h->device_bytes);
+        h->q.release();
     }
     delete h;
 }
@@ -346,15 +321,7 @@ extern "C" int rsem_gmap_convert(rsem_gmap* h, int32_t mates, int64_t n_alignmen
         }
     }
     uint64_t budget = kDefaultBatchItems;
-    if (const char* e = getenv("RSEM_GMAP_BATCH_ITEMS")) {  // a test and measurement knob, read at call time
-        char* end = nullptr;
-        const long long v = strtoll(e, &end, 10);
-        if (end == e || *end || v < 1) {
-            rsem::set_last_error("RSEM_GMAP_BATCH_ITEMS = '%s': a whole number from 1 on is expected", e);
-            return RSEM_ERR_INVALID;
-        }
-        budget = (uint64_t)v;
-    }
+    if (int rc = rsem::env_whole("RSEM_GMAP_BATCH_ITEMS", 1, LLONG_MAX, &budget)) return rc;  // a test and measurement knob, read at call time
     if (info) {
         memset(info, 0, sizeof(*info));
         info->batch_items = budget;

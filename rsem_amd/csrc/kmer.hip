@@ -20,38 +20,19 @@
 #include <cstdlib>
 #include <vector>
 
-#include "common.hpp"
 #include "kmer_block.hpp"
+#include "stage_util.hpp"
 
 namespace {
 
 using namespace rsem_kmer;
+using rsem::blocks256;
 
 constexpr int kTileThreads = 256;
 constexpr int kPerLane = kLaneStarts;
 constexpr int kTile = kTileThreads * kPerLane;  // starts per workgroup
 constexpr int kMaxK = 32768;                    // the halo of a tile stays within 32 KiB of LDS
 constexpr uint64_t kMaxBatchItems = 0x7fffffffull;  // the indices inside a batch are 32-bit
-
-struct DevMem {  // frees what it owns on scope exit
-    std::vector<void*> ptrs;
-    ~DevMem() { for (void* p : ptrs) (void)hipFree(p); }
-    template <class T> hipError_t alloc(T** p, size_t n) {
-        hipError_t e = hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-};
-struct EventGuard {
-    hipEvent_t e = nullptr;
-    ~EventGuard() { if (e) (void)hipEventDestroy(e); }
-    hipError_t create() { return hipEventCreate(&e); }
-};
-struct StreamGuard {
-    hipStream_t s = nullptr;
-    ~StreamGuard() { if (s) (void)hipStreamDestroy(s); }
-    hipError_t create() { return hipStreamCreate(&s); }
-};
 
 enum { kHist = 0, kCount = 1, kEmit = 2 };
 
@@ -174,8 +155,6 @@ __global__ void __launch_bounds__(256) k_count(const uint32_t* __restrict__ gid,
     if (t >= 0 && (boundary >> lane & 1)) atomicAdd(shared + t, (uint32_t)run_length(boundary, lane, 64));
 }
 
-inline uint32_t blocks256(uint64_t n) { return (uint32_t)((n + 255) / 256); }
-
 template <class ValT>
 int run(int device, int32_t M, const uint64_t* seq_off, const uint8_t* codes, int32_t k, uint64_t n_kmers, uint64_t budget_env,
         uint32_t* shared, rsem_kmer_info* info) {
@@ -197,12 +176,10 @@ int run(int device, int32_t M, const uint64_t* seq_off, const uint8_t* codes, in
     soff[M] = Ls;
 
     RSEM_HIP_TRY(hipSetDevice(device));
-    StreamGuard sg;
-    RSEM_HIP_TRY(sg.create());
-    hipStream_t st = sg.s;
-    EventGuard e0, e1, e2;
-    RSEM_HIP_TRY(e0.create()); RSEM_HIP_TRY(e1.create()); RSEM_HIP_TRY(e2.create());
-    DevMem mem;
+    rsem::StageQueue q;
+    RSEM_HIP_TRY(q.create());
+    hipStream_t st = q.st;
+    rsem::DevMem mem;
     uint8_t* d_sep = nullptr;
     uint64_t* d_soff = nullptr;
     uint32_t *d_shared = nullptr, *d_tile_cnt = nullptr, *d_tile_off = nullptr;
@@ -212,13 +189,13 @@ int run(int device, int32_t M, const uint64_t* seq_off, const uint8_t* codes, in
     RSEM_HIP_TRY(mem.alloc(&d_tile_cnt, (size_t)ntiles + 1));
     RSEM_HIP_TRY(mem.alloc(&d_tile_off, (size_t)ntiles + 1));
 
-    RSEM_HIP_TRY(hipEventRecord(e0.e, st));
+    RSEM_HIP_TRY(q.upload_begin());
     RSEM_HIP_TRY(hipMemsetAsync(d_sep, kSep, sep_bytes, st));
     RSEM_HIP_TRY(hipMemcpyAsync(d_sep, sep.data(), (size_t)Ls, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemcpyAsync(d_soff, soff.data(), ((size_t)M + 1) * 8, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemsetAsync(d_shared, 0, (size_t)M * 4, st));
     RSEM_HIP_TRY(hipMemsetAsync(d_tile_cnt, 0, ((size_t)ntiles + 1) * 4, st));
-    RSEM_HIP_TRY(hipEventRecord(e1.e, st));
+    RSEM_HIP_TRY(q.upload_end());
     RSEM_HIP_TRY(hipStreamSynchronize(st));
 
     // what fits: keys and values, each twice -- the two halves the library's sort goes back and forth between (its DoubleBuffer
@@ -342,14 +319,13 @@ int run(int device, int32_t M, const uint64_t* seq_off, const uint8_t* codes, in
         RSEM_HIP_TRY(hipGetLastError());
         n_groups += groups;
     }
-    RSEM_HIP_TRY(hipEventRecord(e2.e, st));
+    RSEM_HIP_TRY(q.kernels_end());
     RSEM_HIP_TRY(hipMemcpyAsync(shared, d_shared, (size_t)M * 4, hipMemcpyDeviceToHost, st));
     RSEM_HIP_TRY(hipStreamSynchronize(st));
     RSEM_HIP_TRY(hipGetLastError());
     if (info) {
-        float up = 0, kern = 0;
-        RSEM_HIP_TRY(hipEventElapsedTime(&up, e0.e, e1.e));
-        RSEM_HIP_TRY(hipEventElapsedTime(&kern, e1.e, e2.e));
+        double up = 0, kern = 0;
+        if (int rc = q.add_laps(up, kern)) return rc;
         info->n_groups = n_groups;
         info->n_batches = (int32_t)batches.size();
         info->batch_items = budget;
@@ -382,15 +358,7 @@ extern "C" int rsem_kmer_shared_counts(int device, int32_t M, const uint64_t* se
     for (uint64_t i = 0; i < L; i++) seen |= (uint8_t)(codes[i] > 4);
     RSEM_REQUIRE(!seen, "rsem_kmer_shared_counts: codes must be 0 .. 4 (A C G T N)");
     uint64_t budget_env = 0;
-    if (const char* e = getenv("RSEM_KMER_BATCH_ITEMS")) {  // a test and measurement knob, read at call time
-        char* end = nullptr;
-        const long long v = strtoll(e, &end, 10);
-        if (end == e || *end || v < 1) {
-            rsem::set_last_error("RSEM_KMER_BATCH_ITEMS = '%s': a whole number from 1 on is expected", e);
-            return RSEM_ERR_INVALID;
-        }
-        budget_env = (uint64_t)v;
-    }
+    if (int rc = rsem::env_whole("RSEM_KMER_BATCH_ITEMS", 1, LLONG_MAX, &budget_env)) return rc;  // a test and measurement knob, read at call time
     if (info) {
         memset(info, 0, sizeof(*info));
         info->n_kmers = n_kmers;

@@ -22,28 +22,15 @@
 #include <mutex>
 #include <vector>
 
-#include "common.hpp"
 #include "pairscan_block.hpp"
+#include "stage_util.hpp"
 
 using namespace rsem_pairk;
 
 namespace {
 
-struct Buf {  // a device buffer that only grows
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t bytes, size_t& total) {
-        if (bytes <= cap) return hipSuccess;
-        const size_t want = bytes + bytes / 2 + 256;
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, want);
-        if (e != hipSuccess) return e;
-        if (p) { (void)hipFree(p); total -= cap; }
-        p = q; cap = want; total += want;
-        return hipSuccess;
-    }
-    template <class T> T* as() const { return (T*)p; }
-};
+using rsem::blocks256;
+using Buf = rsem::GrowBuf<2>;  // a device buffer that only grows
 
 enum { B_NOFF, B_NAMES, B_FLAG, B_TID, B_POS, B_MPOS, B_MARK, B_RUN, B_WA, B_WB, B_CA, B_CB, B_OPEN, B_ORD, B_GOFF, B_PERM, B_BOTH, B_SW, B_SWS, B_SMALL, B_LARGE, B_TMP,
        B_COUNT };
@@ -54,8 +41,7 @@ struct rsem_pairscan {
     int device = 0;
     bool on_device = false, ended = false;
     unsigned long long* d_verdict = nullptr;
-    hipStream_t st = nullptr;
-    hipEvent_t ea = nullptr, eb = nullptr, ec = nullptr;
+    rsem::StageQueue q;
     Buf buf[B_COUNT];
     size_t device_bytes = 0;
     std::mutex mu;
@@ -119,27 +105,16 @@ __global__ void __launch_bounds__(kGroupThreads) k_pairscan_rank(Recs R, uint32_
     }
 }
 
-inline uint32_t blocks256(uint64_t n) { return (uint32_t)((n + 255) / 256); }
-
 // RSEM_PAIRSCAN_BATCH_ITEMS, read at every call
 int read_budget(uint64_t& budget) {
     budget = kDefaultBatchItems;
-    if (const char* e = getenv("RSEM_PAIRSCAN_BATCH_ITEMS")) {
-        char* end = nullptr;
-        const long long v = strtoll(e, &end, 10);
-        if (end == e || *end || v < 1) { rsem::set_last_error("RSEM_PAIRSCAN_BATCH_ITEMS = '%s': a whole number from 1 on is expected", e); return RSEM_ERR_INVALID; }
-        budget = (uint64_t)v;
-    }
-    return RSEM_OK;
+    return rsem::env_whole("RSEM_PAIRSCAN_BATCH_ITEMS", 1, LLONG_MAX, &budget);
 }
 
 int to_device(rsem_pairscan* h) {
     RSEM_HIP_TRY(hipSetDevice(h->device));
     if (h->on_device) return RSEM_OK;
-    RSEM_HIP_TRY(hipStreamCreate(&h->st));
-    RSEM_HIP_TRY(hipEventCreate(&h->ea));
-    RSEM_HIP_TRY(hipEventCreate(&h->eb));
-    RSEM_HIP_TRY(hipEventCreate(&h->ec));
+    RSEM_HIP_TRY(h->q.create());
     RSEM_HIP_TRY(hipMalloc((void**)&h->d_verdict, 8));
     h->device_bytes += 8;
     h->on_device = true;
@@ -159,24 +134,24 @@ int run_batch(rsem_pairscan* h, const Call& c, uint64_t lo, uint64_t n, uint64_t
               int64_t& fail_record, rsem_pairscan_verdict* v, double& upload_ms, double& kernel_ms) {
     const uint64_t nb = c.name_off[lo + n] - c.name_off[lo];
     size_t t1 = 0, t2 = 0, t3 = 0;
-    RSEM_HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, t1, (const uint32_t*)nullptr, (uint32_t*)nullptr, RunCount(), (int)n, h->st));
-    RSEM_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)(n + 1), h->st));
-    RSEM_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, t3, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, h->st));
+    RSEM_HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, t1, (const uint32_t*)nullptr, (uint32_t*)nullptr, RunCount(), (int)n, h->q.st));
+    RSEM_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)(n + 1), h->q.st));
+    RSEM_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, t3, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, h->q.st));
     const size_t w4 = (size_t)(n + 1) * 4, w8 = (size_t)(n + 1) * 8;
     const size_t need[B_COUNT] = {w8, (size_t)nb, w4, w4, w4, w4, w4, w4, w8, w8, w8, w8, w4, w4, w4, w4, w4, w8, w8, w4, w4, std::max(t1, std::max(t2, t3))};
     for (int b = 0; b < B_COUNT; b++) RSEM_HIP_TRY(h->buf[b].need(std::max<size_t>(need[b], 8), h->device_bytes));
     auto U64 = [&](int b) { return h->buf[b].as<uint64_t>(); };
     auto U32 = [&](int b) { return h->buf[b].as<uint32_t>(); };
     auto I32 = [&](int b) { return h->buf[b].as<int32_t>(); };
-    hipStream_t st = h->st;
-    RSEM_HIP_TRY(hipEventRecord(h->ea, st));
+    hipStream_t st = h->q.st;
+    RSEM_HIP_TRY(h->q.upload_begin());
     RSEM_HIP_TRY(hipMemcpyAsync(U64(B_NOFF), c.name_off + lo, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemcpyAsync(h->buf[B_NAMES].p, c.names + c.name_off[lo], (size_t)nb, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemcpyAsync(U32(B_FLAG), c.flag + lo, (size_t)n * 4, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemcpyAsync(I32(B_TID), c.tid + lo, (size_t)n * 4, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemcpyAsync(I32(B_POS), c.pos + lo, (size_t)n * 4, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemcpyAsync(I32(B_MPOS), c.mpos + lo, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    RSEM_HIP_TRY(hipEventRecord(h->eb, st));
+    RSEM_HIP_TRY(h->q.upload_end());
 
     const Recs R{U64(B_NOFF), h->buf[B_NAMES].as<uint8_t>(), c.name_off[lo], U32(B_FLAG), I32(B_TID), I32(B_POS), I32(B_MPOS), (int64_t)n};
     const Scans S{U32(B_ORD), U64(B_CA), U64(B_CB)};
@@ -214,7 +189,7 @@ int run_batch(rsem_pairscan* h, const Call& c, uint64_t lo, uint64_t n, uint64_t
                            U32(B_BOTH), (uint32_t)lo, U32(B_PERM));
         v->n_launches += 1;
     }
-    RSEM_HIP_TRY(hipEventRecord(h->ec, st));
+    RSEM_HIP_TRY(h->q.kernels_end());
     if (word == kNoVerdict) RSEM_HIP_TRY(hipMemcpyAsync(c.perm_out + lo, U32(B_PERM), (size_t)n * 4, hipMemcpyDeviceToHost, st));
     else {
         const uint64_t fg = word >> 8;
@@ -228,12 +203,7 @@ int run_batch(rsem_pairscan* h, const Call& c, uint64_t lo, uint64_t n, uint64_t
     RSEM_HIP_TRY(hipGetLastError());
     n_groups += ng;
     n_sorted += (uint64_t)n_small + n_large;
-    float ms = 0;
-    RSEM_HIP_TRY(hipEventElapsedTime(&ms, h->ea, h->eb));
-    upload_ms += ms;
-    RSEM_HIP_TRY(hipEventElapsedTime(&ms, h->eb, h->ec));
-    kernel_ms += ms;
-    return RSEM_OK;
+    return h->q.add_laps(upload_ms, kernel_ms);
 }
 
 }  // namespace
@@ -253,12 +223,8 @@ extern "C" void rsem_pairscan_destroy(rsem_pairscan* h) {
     if (h->on_device) {
         (void)hipSetDevice(h->device);
         if (h->d_verdict) (void)hipFree(h->d_verdict);
-        for (Buf& b : h->buf)
-            if (b.p) (void)hipFree(b.p);
-        if (h->ea) (void)hipEventDestroy(h->ea);
-        if (h->eb) (void)hipEventDestroy(h->eb);
-        if (h->ec) (void)hipEventDestroy(h->ec);
-        if (h->st) (void)hipStreamDestroy(h->st);
+        for (Buf& b : h->buf) b.release(h->device_bytes);
+        h->q.release();
     }
     delete h;
 }

@@ -16,26 +16,14 @@
 #include <mutex>
 #include <vector>
 
-#include "common.hpp"
 #include "refseq_block.hpp"
+#include "stage_util.hpp"
 
 using namespace rsem_refseqk;
 
 namespace {
 
-struct Buf {  // a device buffer that only grows
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t bytes, size_t& total) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) { (void)hipFree(p); total -= cap; p = nullptr; cap = 0; }
-        const size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) { cap = want; total += want; }
-        return e;
-    }
-    template <class T> T* as() const { return (T*)p; }
-};
+using Buf = rsem::GrowBuf<8>;  // a device buffer that only grows
 
 enum { B_RAW, B_BASES, B_LO, B_HI, B_KEEP, B_BAD, B_BASE, B_END, B_COUNT_T, B_START_T, B_TMP, B_CUM, B_SRC, B_DST, B_FLAGS, B_N };
 
@@ -46,8 +34,7 @@ struct rsem_refseq {
     uint64_t store_bytes = 0, store_pad = 0;
     bool on_device = false;
     void* d_store = nullptr;  // the allocation: store_pad + store_bytes (+ 16)
-    hipStream_t st = nullptr;
-    hipEvent_t ea = nullptr, eb = nullptr, ec = nullptr;
+    rsem::StageQueue q;
     Buf buf[B_N];
     size_t device_bytes = 0;
     // the batch that is resident
@@ -99,16 +86,13 @@ int env_u64(const char* name, uint64_t lo, uint64_t multiple, const char* what, 
 int to_device(rsem_refseq* h) {
     RSEM_HIP_TRY(hipSetDevice(h->device));
     if (h->on_device) return RSEM_OK;
-    RSEM_HIP_TRY(hipStreamCreate(&h->st));
-    RSEM_HIP_TRY(hipEventCreate(&h->ea));
-    RSEM_HIP_TRY(hipEventCreate(&h->eb));
-    RSEM_HIP_TRY(hipEventCreate(&h->ec));
+    RSEM_HIP_TRY(h->q.create());
     const size_t bytes = (size_t)(h->store_pad + h->store_bytes + 16);
     RSEM_HIP_TRY(hipMalloc(&h->d_store, bytes));
     h->device_bytes += bytes;
     // the runtime loads this translation unit's code object at its first launch (tens of milliseconds): paid here, not inside the first batch's kernel time
-    hipLaunchKernelGGL(k_refseq_loaded, dim3(1), dim3(1), 0, h->st);
-    RSEM_HIP_TRY(hipStreamSynchronize(h->st));
+    hipLaunchKernelGGL(k_refseq_loaded, dim3(1), dim3(1), 0, h->q.st);
+    RSEM_HIP_TRY(hipStreamSynchronize(h->q.st));
     h->on_device = true;
     return RSEM_OK;
 }
@@ -143,12 +127,8 @@ extern "C" void rsem_refseq_destroy(rsem_refseq* h) {
     if (h->on_device) {
         (void)hipSetDevice(h->device);
         if (h->d_store) (void)hipFree(h->d_store);
-        for (Buf& b : h->buf)
-            if (b.p) (void)hipFree(b.p);
-        if (h->ea) (void)hipEventDestroy(h->ea);
-        if (h->eb) (void)hipEventDestroy(h->eb);
-        if (h->ec) (void)hipEventDestroy(h->ec);
-        if (h->st) (void)hipStreamDestroy(h->st);
+        for (Buf& b : h->buf) b.release(h->device_bytes);
+        h->q.release();
     }
     delete h;
 }
@@ -203,13 +183,13 @@ extern "C" int rsem_refseq_load(rsem_refseq* h, int32_t mode, const uint8_t* raw
     for (uint32_t i = 0; i < n; i++) { lo[i] = body_lo[first + i] - origin; hi[i] = body_hi[first + i] - origin; kp[i] = keep ? keep[first + i] != 0 : 1; }
 
     size_t tmp_bytes = 0;
-    RSEM_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)(n_tiles + 1), h->st));
+    RSEM_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)(n_tiles + 1), h->q.st));
     const size_t need[B_TMP + 1] = {(size_t)raw_len + 32, (size_t)kept_raw + 2 * kPad + 16, (size_t)n * 8, (size_t)n * 8, (size_t)n + 8, (size_t)n * 8, (size_t)n * 8,
                                     (size_t)n * 8, (size_t)(n_tiles + 1) * 8, (size_t)(n_tiles + 1) * 8, tmp_bytes};
     for (int b = 0; b <= B_TMP; b++) RSEM_HIP_TRY(h->buf[b].need(need[b], h->device_bytes));
     auto U64 = [&](int b) { return h->buf[b].as<uint64_t>(); };
-    hipStream_t st = h->st;
-    RSEM_HIP_TRY(hipEventRecord(h->ea, st));
+    hipStream_t st = h->q.st;
+    RSEM_HIP_TRY(h->q.upload_begin());
     if (raw_len) RSEM_HIP_TRY(hipMemcpyAsync(h->buf[B_RAW].p, raw + origin, (size_t)raw_len, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemcpyAsync(U64(B_LO), lo.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemcpyAsync(U64(B_HI), hi.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
@@ -218,7 +198,7 @@ extern "C" int rsem_refseq_load(rsem_refseq* h, int32_t mode, const uint8_t* raw
     RSEM_HIP_TRY(hipMemsetAsync(U64(B_BASE), 0, (size_t)n * 8, st));
     RSEM_HIP_TRY(hipMemsetAsync(U64(B_END), 0, (size_t)n * 8, st));
     RSEM_HIP_TRY(hipMemsetAsync(U64(B_COUNT_T) + n_tiles, 0, 8, st));
-    RSEM_HIP_TRY(hipEventRecord(h->eb, st));
+    RSEM_HIP_TRY(h->q.upload_end());
     const Batch B{h->buf[B_RAW].as<uint8_t>(), raw_len, n, U64(B_LO), U64(B_HI), h->buf[B_KEEP].as<uint8_t>(), (uint32_t)mode};
     uint8_t* bases = h->buf[B_BASES].as<uint8_t>() + kPad;
     std::vector<uint64_t> base(n), end(n), bd(n);
@@ -239,7 +219,7 @@ extern "C" int rsem_refseq_load(rsem_refseq* h, int32_t mode, const uint8_t* raw
         hipLaunchKernelGGL(k_refseq_write, dim3(blocks), dim3(kThreads), 0, st, B, n_tiles, U64(B_START_T), bases, U64(B_BASE), U64(B_END));
         h->info.n_launches += 3;
     }
-    RSEM_HIP_TRY(hipEventRecord(h->ec, st));
+    RSEM_HIP_TRY(h->q.kernels_end());
     RSEM_HIP_TRY(hipMemcpyAsync(base.data(), U64(B_BASE), (size_t)n * 8, hipMemcpyDeviceToHost, st));
     RSEM_HIP_TRY(hipMemcpyAsync(end.data(), U64(B_END), (size_t)n * 8, hipMemcpyDeviceToHost, st));
     RSEM_HIP_TRY(hipMemcpyAsync(bd.data(), U64(B_BAD), (size_t)n * 8, hipMemcpyDeviceToHost, st));
@@ -263,11 +243,7 @@ extern "C" int rsem_refseq_load(rsem_refseq* h, int32_t mode, const uint8_t* raw
     }
     h->res_n = n;
     *n_taken = n;
-    float ms = 0;
-    RSEM_HIP_TRY(hipEventElapsedTime(&ms, h->ea, h->eb));
-    h->info.upload_ms += ms;
-    RSEM_HIP_TRY(hipEventElapsedTime(&ms, h->eb, h->ec));
-    h->info.kernel_ms += ms;
+    if (int rc = h->q.add_laps(h->info.upload_ms, h->info.kernel_ms)) return rc;
     h->info.n_batches += 1;
     h->info.n_records += n;
     h->info.raw_bytes += raw_len;
@@ -315,25 +291,21 @@ extern "C" int rsem_refseq_gather(rsem_refseq* h, int64_t n_segments, const int6
     const size_t need[4] = {(n + 1) * 8, n * 8, n * 8, n * 4};
     for (int b = 0; b < 4; b++) RSEM_HIP_TRY(h->buf[B_CUM + b].need(need[b], h->device_bytes));
     RSEM_HIP_TRY(h->buf[B_BASES].need(2 * kPad + 16, h->device_bytes));  // (fills alone: no load came before)
-    hipStream_t st = h->st;
-    RSEM_HIP_TRY(hipEventRecord(h->ea, st));
+    hipStream_t st = h->q.st;
+    RSEM_HIP_TRY(h->q.upload_begin());
     RSEM_HIP_TRY(hipMemcpyAsync(h->buf[B_CUM].p, cum.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemcpyAsync(h->buf[B_SRC].p, sa.data(), n * 8, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemcpyAsync(h->buf[B_DST].p, dst, n * 8, hipMemcpyHostToDevice, st));
     RSEM_HIP_TRY(hipMemcpyAsync(h->buf[B_FLAGS].p, flags, n * 4, hipMemcpyHostToDevice, st));
-    RSEM_HIP_TRY(hipEventRecord(h->eb, st));
+    RSEM_HIP_TRY(h->q.upload_end());
     const Segments S{(uint64_t)n, h->buf[B_CUM].as<uint64_t>(), h->buf[B_SRC].as<uint64_t>(), h->buf[B_DST].as<uint64_t>(), h->buf[B_FLAGS].as<uint32_t>()};
     const uint64_t blocks = (cum[n] + kGroupSpan - 1) / kGroupSpan;
     RSEM_REQUIRE(blocks < (1ull << 31), "rsem_refseq_gather: 2^45 bytes or more in one call");
     hipLaunchKernelGGL(k_refseq_gather, dim3((uint32_t)blocks), dim3(kThreads), 0, st, S, h->buf[B_BASES].as<uint8_t>() + kPad, (uint8_t*)h->d_store + h->store_pad);
-    RSEM_HIP_TRY(hipEventRecord(h->ec, st));
+    RSEM_HIP_TRY(h->q.kernels_end());
     RSEM_HIP_TRY(hipStreamSynchronize(st));
     RSEM_HIP_TRY(hipGetLastError());
-    float ms = 0;
-    RSEM_HIP_TRY(hipEventElapsedTime(&ms, h->ea, h->eb));
-    h->info.upload_ms += ms;
-    RSEM_HIP_TRY(hipEventElapsedTime(&ms, h->eb, h->ec));
-    h->info.kernel_ms += ms;
+    if (int rc = h->q.add_laps(h->info.upload_ms, h->info.kernel_ms)) return rc;
     h->info.n_launches += 1;
     h->info.n_segments += n;
     h->info.gathered_bytes += cum[n];
@@ -348,14 +320,11 @@ extern "C" int rsem_refseq_download(rsem_refseq* h, uint64_t offset, uint64_t by
     RSEM_REQUIRE(out, "rsem_refseq_download: out must not be NULL");
     std::lock_guard<std::mutex> lock(h->mu);
     if (int rc = to_device(h)) return rc;
-    RSEM_HIP_TRY(hipEventRecord(h->ea, h->st));
-    RSEM_HIP_TRY(hipMemcpyAsync(out, (const uint8_t*)h->d_store + h->store_pad + offset, (size_t)bytes, hipMemcpyDeviceToHost, h->st));
-    RSEM_HIP_TRY(hipEventRecord(h->eb, h->st));
-    RSEM_HIP_TRY(hipStreamSynchronize(h->st));
-    float ms = 0;
-    RSEM_HIP_TRY(hipEventElapsedTime(&ms, h->ea, h->eb));
-    h->info.download_ms += ms;
-    return RSEM_OK;
+    RSEM_HIP_TRY(h->q.upload_begin());  // (the first lap, around a copy the other way)
+    RSEM_HIP_TRY(hipMemcpyAsync(out, (const uint8_t*)h->d_store + h->store_pad + offset, (size_t)bytes, hipMemcpyDeviceToHost, h->q.st));
+    RSEM_HIP_TRY(h->q.upload_end());
+    RSEM_HIP_TRY(hipStreamSynchronize(h->q.st));
+    return h->q.add_upload_lap(h->info.download_ms);
 }
 
 extern "C" int rsem_refseq_get_info(rsem_refseq* h, rsem_refseq_info* info) {

@@ -190,3 +190,22 @@ def test_library_refuses_invalid_arguments_without_a_device(monkeypatch):
     keep, info = capi.alncheck_unique([0], b"\0", [])
     assert len(keep) == 0 and info["n_batches"] == 0 and info["device_bytes"] == 0
     assert L.rsem_hip_abi_version() == 4
+
+
+def test_library_takes_the_knobs_as_strtoll_reads_them(monkeypatch):
+    """the accept side of RSEM_ALNCHECK_BATCH_ITEMS (leading white space, a sign and leading zeros are part of a whole number) and
+    both sides of the upper end of RSEM_ALNCHECK_HASH_BITS"""
+    from rsem_amd import capi
+    ck = capi.Alncheck([100, 50])
+    for good in ("7", " 7", "+7", "007"):
+        monkeypatch.setenv("RSEM_ALNCHECK_BATCH_ITEMS", good)
+        v = ck.push(**ar.pack([]))  # nothing to check: no device needed
+        assert v["batch_items"] == 7 and v["n_batches"] == 0, good
+        keep, info = capi.alncheck_unique([0], b"\0", [])
+        assert len(keep) == 0 and info["batch_items"] == 7, good
+    monkeypatch.setenv("RSEM_ALNCHECK_HASH_BITS", "64")
+    assert ck.push(**ar.pack([]))["batch_items"] == 7
+    monkeypatch.setenv("RSEM_ALNCHECK_HASH_BITS", "65")
+    e = pytest.raises(capi.RsemHipError, lambda: ck.push(**ar.pack([])))
+    assert e.value.status == INVALID and "RSEM_ALNCHECK_HASH_BITS" in str(e.value) and "from 1 to 64" in str(e.value)
+    ck.close()

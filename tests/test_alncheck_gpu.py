@@ -223,7 +223,9 @@ def repeats():
 @pytest.mark.parametrize("budget", [None, 1, 7])
 @pytest.mark.parametrize("bits", [None, 64, 3, 1])
 def test_a_name_that_comes_back(monkeypatch, bits, budget):
-    """with one and three hash bits every bisection lands in a crowd of equal hashes: the bytes decide, and the verdicts stay the same"""
+    """with one and three hash bits every bisection lands in a crowd of equal hashes: the bytes decide, and the verdicts stay the same.
+    With a batch per unit the resident arrays, first sized for one group (268 bytes: 33 groups), are regrown many times on the way to
+    300 groups: the name that is found again was carried across every regrowth (GrowBuf's keep)"""
     if bits:
         monkeypatch.setenv("RSEM_ALNCHECK_HASH_BITS", str(bits))
     if budget:

@@ -234,3 +234,12 @@ def test_library_refuses_invalid_arguments_without_a_device(monkeypatch):
         assert np.array_equal(dr.bits(got), dr.bits(before)) and info["n_entries"] == 0 and info["n_launches"] == 0 and info["device_bytes"] == 0
     got, info = capi.depth_accumulate(0, np.zeros(1, np.uint64), np.zeros(1, np.uint32), np.ones(1))  # no base
     assert len(got) == 0 and info["n_batches"] == 0
+
+
+def test_library_takes_the_batch_knob_as_strtoll_reads_it(monkeypatch):
+    """the accept side of RSEM_DEPTH_BATCH_ITEMS: leading white space, a sign and leading zeros are part of a whole number"""
+    from rsem_amd import capi
+    for good in ("7", " 7", "+7", "007"):
+        monkeypatch.setenv("RSEM_DEPTH_BATCH_ITEMS", good)
+        got, info = capi.depth_accumulate(3, np.zeros(0, np.uint64), np.zeros(0, np.uint32), np.zeros(0))  # no block: no device needed
+        assert len(got) == 3 and info["batch_items"] == 7 and info["n_batches"] == 0, good

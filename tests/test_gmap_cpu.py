@@ -261,3 +261,14 @@ def test_library_refuses_invalid_arguments_without_a_device(monkeypatch):
     assert o["info"]["n_alignments_out"] == 0 and o["info"]["n_batches"] == 0 and o["info"]["device_bytes"] == 0 and len(o["cigar"]) == 0
     g.close()
     assert capi.lib().rsem_hip_abi_version() == 4
+
+
+def test_library_takes_the_batch_knob_as_strtoll_reads_it(monkeypatch):
+    """the accept side of RSEM_GMAP_BATCH_ITEMS: leading white space, a sign and leading zeros are part of a whole number"""
+    from rsem_amd import capi
+    g = small_gmap(capi)
+    for good in ("7", " 7", "+7", "007"):
+        monkeypatch.setenv("RSEM_GMAP_BATCH_ITEMS", good)
+        o = g.convert(1, [0], [], [], [], [], [])  # nothing to convert: no device needed
+        assert o["info"]["batch_items"] == 7 and o["info"]["n_batches"] == 0, good
+    g.close()

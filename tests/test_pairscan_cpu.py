@@ -215,6 +215,17 @@ def test_library_refuses_invalid_arguments_without_a_device(monkeypatch):
     assert L.rsem_hip_abi_version() == 4
 
 
+def test_library_takes_the_batch_knob_as_strtoll_reads_it(monkeypatch):
+    """the accept side of RSEM_PAIRSCAN_BATCH_ITEMS: leading white space, a sign and leading zeros are part of a whole number"""
+    from rsem_amd import capi
+    ps = capi.Pairscan()
+    for good in ("7", " 7", "+7", "007"):
+        monkeypatch.setenv("RSEM_PAIRSCAN_BATCH_ITEMS", good)
+        perm, v = ps.reorder(**pr.pack([]))  # nothing to order: no device needed
+        assert len(perm) == 0 and v["batch_items"] == 7, good
+    ps.close()
+
+
 # ---- the overlay -------------------------------------------------------------------------------------------------------------------
 
 def test_overlay_copies_the_perl_drivers_that_look_next_to_themselves(program, tmp_path):
