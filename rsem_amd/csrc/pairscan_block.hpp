@@ -66,7 +66,7 @@ RSEM_ALN_FN uint32_t mark_record(const Recs& R, int64_t i) {
     const uint8_t *a = R.name(i), *b = R.name(i - 1);
     const uint32_t la = R.name_len(i), ca = canonical_len(a, la);
     if (!same_bytes(a, ca, b, canonical_len(b, R.name_len(i - 1)))) return kHard | paired;
-    return la > ca ? (kSoft | paired) : 0u;
+    return la > ca && a[ca] ? (kSoft | paired) : 0u;  // (a NUL ends the raw name too: the reference compares C strings, :119)
 }
 
 // the scan's operator: a count that starts again at every hard record (kSoft is dropped).  After the inclusive scan, word i &

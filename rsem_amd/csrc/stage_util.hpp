@@ -3,6 +3,7 @@
 // events around a batch's upload and its kernels, the whole-number knobs.  Nothing here launches a kernel.
 #pragma once
 #include <algorithm>
+#include <cerrno>
 #include <climits>
 #include <cstdlib>
 #include <vector>
@@ -105,13 +106,14 @@ struct StageQueue {
 };
 
 // A knob that holds a whole number from lo to hi, read when it is called.  Unset: *value stays as it is.  Anything but such a
-// number is an error, not silently the default.
+// number is an error, not silently the default -- a value strtoll clamps to the ends of long long (ERANGE) too.
 inline int env_whole(const char* name, long long lo, long long hi, uint64_t* value) {
     const char* e = getenv(name);
     if (!e) return RSEM_OK;
     char* end = nullptr;
+    errno = 0;
     const long long v = strtoll(e, &end, 10);
-    if (end == e || *end || v < lo || v > hi) {
+    if (end == e || *end || errno == ERANGE || v < lo || v > hi) {
         if (hi == LLONG_MAX) set_last_error("%s = '%s': a whole number from %lld on is expected", name, e, lo);
         else set_last_error("%s = '%s': a whole number from %lld to %lld is expected", name, e, lo, hi);
         return RSEM_ERR_INVALID;

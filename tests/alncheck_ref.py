@@ -62,7 +62,7 @@ def record_bytes(r):
 
 def canonical(name):
     for i, c in enumerate(name):
-        if c in b" \t\n\r\f\v":
+        if c in b" \t\n\r\f\v\0":  # (bam_get_canonical_name works on the C string: a NUL ends it)
             return name[:i]
     return name
 

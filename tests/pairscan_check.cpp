@@ -7,6 +7,7 @@
 // sanitizer reports.  Built with AddressSanitizer and UBSan (tests/test_pairscan_cpu.py).  Never part of the product.
 //
 //   pairscan_check <N> <alignments> <out.bam>
+//   pairscan_check records <file>      rsem_pairscan_reorder on records given as text, the verdict and the permutation printed
 // Build: hipcc (host compilation of the HIP headers simt_emu.hpp pulls in) -DRSEM_EMU -fsanitize=address,undefined -fno-gpu-sanitize
 #include "simt_emu.hpp"
 
@@ -152,10 +153,46 @@ extern "C" int rsem_pairscan_reorder(rsem_pairscan* h, int64_t n_records, const 
     return RSEM_OK;
 }
 
+// records <file>: the arrays of rsem_pairscan_reorder as text, a record a line -- the name in hexadecimal, flag, tid, pos, mpos -- for what
+// no alignment file carries (a NUL inside a name, a tid at the ends of 32 bits).  Prints the verdict's words, then the permutation.
+int records_main(const char* path) {
+    FILE* f = fopen(path, "r");
+    if (!f) { fprintf(stderr, "cannot open %s\n", path); return 2; }
+    std::vector<uint64_t> name_off{0};
+    std::vector<uint8_t> names;
+    std::vector<uint32_t> flag;
+    std::vector<int32_t> tid, pos, mpos;
+    char hex[2 * 300];
+    long long fl, t, p, m;
+    while (fscanf(f, "%599s %lld %lld %lld %lld", hex, &fl, &t, &p, &m) == 5) {
+        for (size_t k = 0; hex[k] && hex[k + 1]; k += 2) {
+            unsigned v = 0;
+            sscanf(hex + k, "%2x", &v);
+            names.push_back((uint8_t)v);
+        }
+        name_off.push_back(names.size());
+        flag.push_back((uint32_t)fl); tid.push_back((int32_t)t); pos.push_back((int32_t)p); mpos.push_back((int32_t)m);
+    }
+    fclose(f);
+    names.shrink_to_fit();  // exactly the names' bytes: a read behind them is a heap overflow
+    rsem_pairscan* h = nullptr;
+    rsem_pairscan_create(&h, 0);
+    std::vector<uint32_t> perm(flag.size());
+    rsem_pairscan_verdict v;
+    const int rc = rsem_pairscan_reorder(h, (int64_t)flag.size(), name_off.data(), names.data(), flag.data(), tid.data(), pos.data(), mpos.data(), 1, perm.data(), &v);
+    rsem_pairscan_destroy(h);
+    if (rc) { fprintf(stderr, "rsem_pairscan_reorder: %d (%s)\n", rc, g_error.c_str()); return 1; }
+    printf("%d %lld %lld %llu %d %llu\n", v.code, (long long)v.group, (long long)v.group_record, (unsigned long long)v.n_groups, v.n_batches, (unsigned long long)v.n_sorted_groups);
+    if (!v.code)
+        for (uint32_t x : perm) printf("%u\n", x);
+    return 0;
+}
+
 int main(int argc, char* argv[]) {
     using namespace rsemh;
+    if (argc == 3 && !strcmp(argv[1], "records")) return records_main(argv[2]);
     if (argc != 4) {
-        fprintf(stderr, "usage: pairscan_check <N> <alignments> <out.bam>\n");
+        fprintf(stderr, "usage: pairscan_check <N> <alignments> <out.bam> | records <file>\n");
         return 2;
     }
     AlncheckOptions opt;

@@ -109,7 +109,7 @@ def walk(recs):
                     mixed = j
                 j += 1
         else:
-            while j < n and recs[j].name == q:
+            while j < n and recs[j].name.split(b"\0")[0] == q:  # (:119 compares C strings)
                 j += 1
         out.append((i, j, paired, mixed))
         i = j
@@ -314,7 +314,7 @@ def soft_rule_starts(recs):
     starts, paired_seen = [], 0
     for i, r in enumerate(recs):
         hard = i == 0 or canonical(r.name) != canonical(recs[i - 1].name)
-        soft = not hard and len(r.name) > len(canonical(r.name))
+        soft = not hard and len(r.name.split(b"\0")[0]) > len(canonical(r.name))
         if hard:
             paired_seen = 0
         if hard or (soft and paired_seen == 0):

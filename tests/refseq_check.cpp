@@ -8,6 +8,7 @@
 //   refseq_check synthesis <argv of rsem-synthesis-reference-transcripts>
 //   refseq_check preref <argv of rsem-preref>
 //   refseq_check seams        the load and gather seam shapes of tests/test_refseq_gpu.py against plain loops
+//   refseq_check limits       the byte values, degenerate records and segment counts of tests/refseq_limits.py against the same loops
 // Build: hipcc (host compilation of the HIP headers simt_emu.hpp pulls in) -DRSEM_EMU -fsanitize=address,undefined -fno-gpu-sanitize
 #include "simt_emu.hpp"
 
@@ -320,6 +321,252 @@ int seams() {
     return g_fail ? 1 : 0;
 }
 
+// ---- the limit shapes of tests/refseq_limits.py against the same plain loops ------------------------------------------------------
+
+struct Seg { int64_t src; uint32_t first, len; uint64_t dst; uint32_t flags; };
+
+void set_budget(uint64_t b) {  // 0: unset
+    if (b) setenv("RSEM_REFSEQ_BATCH_BYTES", std::to_string(b).c_str(), 1); else unsetenv("RSEM_REFSEQ_BATCH_BYTES");
+}
+
+std::string any_letters(size_t n, size_t width, uint32_t seed) {  // A-Z and a-z, a line end after every `width` of them (0: none)
+    std::string s;
+    size_t col = 0;
+    while (s.size() < n) {
+        if (width && col == width) { s.push_back('\n'); col = 0; continue; }
+        seed = seed * 1664525u + 1013904223u;
+        const uint32_t k = (seed >> 16) % 52;
+        s.push_back((char)(k < 26 ? 'A' + k : 'a' + (k - 26)));
+        col++;
+    }
+    return s;
+}
+
+uint64_t batches_of(const std::vector<uint64_t>& lo, const std::vector<uint64_t>& hi, uint64_t budget) {
+    uint64_t n = 0;
+    for (uint64_t first = 0; first < lo.size(); n++) first = batch_end(lo.data(), hi.data(), lo.size(), first, budget);
+    return n;
+}
+
+// check_load on records given as arrays: every record that has bases (in checked mode: and no bad byte) is copied to a place of its own,
+// at an odd offset of a store that a fill segment has covered before; n_bases, bad, the whole store and the number of batches
+void check_load_arrays(const std::string& raw, const std::vector<uint64_t>& lo, const std::vector<uint64_t>& hi, const std::vector<uint8_t>* keep, int mode, uint64_t budget,
+                       const char* what) {
+    set_budget(budget);
+    const size_t n = lo.size();
+    std::vector<std::string> want(n);
+    std::vector<int64_t> want_bad(n, -1), bad(n, -7);
+    std::vector<uint64_t> nb(n, 77), place(n);
+    uint64_t total = 1;
+    for (size_t r = 0; r < n; r++) {
+        for (uint64_t p = lo[r]; p < hi[r]; p++) {
+            const uint8_t c = (uint8_t)raw[p];
+            if (c == '\n') continue;
+            if (mode == 1 && !plain_letter(c) && want_bad[r] < 0) want_bad[r] = (int64_t)p;
+            if (!keep || (*keep)[r]) want[r].push_back((char)(mode == 1 && plain_letter(c) ? plain_check(c) : c));
+        }
+        place[r] = total;
+        total += ((want[r].size() + 15) & ~15ull) + 16;
+    }
+    total += 16;
+    rsem_refseq* h = nullptr;
+    rsem_refseq_create(&h, 0, total);
+    {
+        const int64_t src = 0;
+        const uint32_t fb = 0, ln = (uint32_t)total, fl = kFlagFill;
+        const uint64_t ds = 0;
+        expect(rsem_refseq_gather(h, 1, &src, &fb, &ln, &ds, &fl) == 0, what);
+    }
+    std::string expected(total, 'A'), got(total, '?');
+    for (int64_t first = 0; first < (int64_t)n;) {
+        int64_t taken = 0;
+        expect(rsem_refseq_load(h, mode, (const uint8_t*)raw.data(), (int64_t)n, lo.data(), hi.data(), keep ? keep->data() : nullptr, first, &taken, nb.data(), bad.data()) == 0, what);
+        if (taken < 1) { expect(false, "nothing taken"); break; }
+        std::vector<int64_t> src;
+        std::vector<uint32_t> fb, ln, fl;
+        std::vector<uint64_t> ds;
+        for (int64_t r = first; r < first + taken; r++)
+            if (nb[r] && bad[r] < 0) { src.push_back(r); fb.push_back(0); ln.push_back((uint32_t)nb[r]); fl.push_back(0); ds.push_back(place[r]); }
+        expect(rsem_refseq_gather(h, (int64_t)src.size(), src.data(), fb.data(), ln.data(), ds.data(), fl.data()) == 0, what);
+        first += taken;
+    }
+    rsem_refseq_download(h, 0, total, (uint8_t*)&got[0]);
+    for (size_t r = 0; r < n; r++) {
+        expect(nb[r] == want[r].size(), what, (long)r, (long)nb[r]);
+        expect(bad[r] == want_bad[r], what, (long)r, (long)bad[r]);
+        if (mode == 0 || want_bad[r] < 0) expected.replace(place[r], want[r].size(), want[r]);
+    }
+    expect(got == expected, what, -1, -1);
+    expect((uint64_t)h->info.n_batches == (budget ? batches_of(lo, hi, budget) : 1), what, -2, h->info.n_batches);
+    rsem_refseq_destroy(h);
+}
+
+// the records loaded batch after batch (raw mode), each batch followed by the segments that read from it; the fill of the whole store first
+void check_gather_arrays(const std::string& raw, const std::vector<uint64_t>& lo, const std::vector<uint64_t>& hi, const std::vector<Seg>& segs, uint64_t size, uint64_t budget,
+                         const char* what) {
+    set_budget(budget);
+    const size_t n = lo.size();
+    std::vector<std::string> bases(n);
+    for (size_t r = 0; r < n; r++)
+        for (uint64_t p = lo[r]; p < hi[r]; p++)
+            if (raw[p] != '\n') bases[r].push_back(raw[p]);
+    std::string want(size, 'A'), got(size, '?');
+    for (const Seg& s : segs)
+        for (uint32_t p = 0; p < s.len; p++)
+            want[s.dst + p] = (s.flags & kFlagFill) ? 'A' : (char)plain_flags((uint8_t)bases[(size_t)s.src][(s.flags & kFlagRC) ? s.first + s.len - 1 - p : s.first + p], s.flags);
+    rsem_refseq* h = nullptr;
+    rsem_refseq_create(&h, 0, size);
+    {
+        const int64_t src = 0;
+        const uint32_t fb = 0, ln = (uint32_t)size, fl = kFlagFill;
+        const uint64_t ds = 0;
+        expect(rsem_refseq_gather(h, 1, &src, &fb, &ln, &ds, &fl) == 0, what);
+    }
+    std::vector<uint64_t> nb(n);
+    std::vector<int64_t> bad(n);
+    for (int64_t first = 0; first < (int64_t)n;) {
+        int64_t taken = 0;
+        expect(rsem_refseq_load(h, 0, (const uint8_t*)raw.data(), (int64_t)n, lo.data(), hi.data(), nullptr, first, &taken, nb.data(), bad.data()) == 0, what);
+        if (taken < 1) { expect(false, "nothing taken"); break; }
+        std::vector<int64_t> src;
+        std::vector<uint32_t> fb, ln, fl;
+        std::vector<uint64_t> ds;
+        for (const Seg& s : segs)
+            if (s.src >= first && s.src < first + taken) { src.push_back(s.src); fb.push_back(s.first); ln.push_back(s.len); fl.push_back(s.flags); ds.push_back(s.dst); }
+        expect(rsem_refseq_gather(h, (int64_t)src.size(), src.data(), fb.data(), ln.data(), ds.data(), fl.data()) == 0, what);
+        first += taken;
+    }
+    rsem_refseq_download(h, 0, size, (uint8_t*)&got[0]);
+    for (size_t r = 0; r < n; r++) expect(nb[r] == bases[r].size(), what, (long)r, (long)nb[r]);
+    expect(got == want, what, -1, -1);
+    rsem_refseq_destroy(h);
+}
+
+int limits() {
+    const uint64_t T = kTile, C = kChunk;
+    // every byte value, raw mode: one record, the 255 values three times; flag sets 0..7 from an odd source offset to odd destinations
+    {
+        std::string body;
+        for (int rep = 0; rep < 3; rep++)
+            for (int v = 0; v < 256; v++)
+                if (v != '\n') body.push_back((char)v);
+        const std::string raw = ">raw\n" + body + "\n";
+        const std::vector<uint64_t> lo{5}, hi{5 + body.size()};
+        std::vector<Seg> segs;
+        uint64_t d = 3;
+        for (uint32_t f = 0; f < 8; f++) { segs.push_back(Seg{0, 1, (uint32_t)body.size() - 2, d, f}); d += body.size() + 5; }
+        for (uint64_t budget : {(uint64_t)0, (uint64_t)1}) {
+            check_load_arrays(raw, lo, hi, nullptr, 0, budget, "every byte, raw");
+            check_gather_arrays(raw, lo, hi, segs, d + 11, budget, "every byte, the flag sets");
+        }
+    }
+    // every byte value, checked mode: 255 records AC?GT, seven bytes apart
+    {
+        std::string raw;
+        std::vector<uint64_t> lo, hi;
+        for (int v = 0; v < 256; v++) {
+            if (v == '\n') continue;
+            raw += ">\n";
+            lo.push_back(raw.size());
+            raw += "AC";
+            raw.push_back((char)v);
+            raw += "GT";
+            hi.push_back(raw.size());
+        }
+        for (uint64_t budget : {(uint64_t)0, (uint64_t)40}) check_load_arrays(raw, lo, hi, nullptr, 1, budget, "every byte, checked");  // (40: six records a batch)
+    }
+    // empty and adjacent bodies
+    {
+        const uint64_t size = 2 * T + 819;
+        std::string raw = any_letters(size, 61, 17);
+        for (uint64_t p = 3060; p < 3090; p++) raw[p] = '\n';
+        raw[2105] = '*';
+        raw[2150] = '-';
+        const std::vector<uint64_t> lo{0, 0, 16, 16, 40, 48, 48, 50, C, C, 1030, 2 * C, 2100, 2112, 2200, 3060, 3090, T, T, 4200, 2 * T, 8253, 8260, 8300, 9000, size};
+        const std::vector<uint64_t> hi{0, 16, 16, 40, 40, 48, 48, C, C, 1030, 2 * C, 2100, 2112, 2200, 3060, 3090, T, T, 4200, 2 * T, 8250, 8253, 8300, 9000, size, size};
+        std::vector<uint8_t> alt(lo.size());
+        for (size_t r = 0; r < alt.size(); r++) alt[r] = (uint8_t)(1 - r % 2);
+        for (int mode = 0; mode < 2; mode++)
+            for (uint64_t budget : {(uint64_t)0, (uint64_t)6, (uint64_t)1}) {  // (6: the smallest body that has a byte, 1024..1030)
+                if (budget == 6 && mode == 0) continue;
+                check_load_arrays(raw, lo, hi, nullptr, mode, budget, "empty and adjacent bodies");
+                check_load_arrays(raw, lo, hi, &alt, mode, budget, "empty and adjacent bodies, keep alternating");
+            }
+        // a call whose only record is empty: no byte uploaded at a multiple of 16
+        const std::vector<uint8_t> none{0};
+        for (uint64_t off : {(uint64_t)32, (uint64_t)21})
+            for (int mode = 0; mode < 2; mode++)
+                for (uint64_t budget : {(uint64_t)0, (uint64_t)1}) {
+                    check_load_arrays(raw.substr(0, 64), {off}, {off}, nullptr, mode, budget, "a lone empty record");
+                    check_load_arrays(raw.substr(0, 64), {off}, {off}, &none, mode, budget, "a lone empty record, not kept");
+                }
+    }
+    // 256 bodies of one byte, a byte apart: eight records to a lane
+    for (int variant = 0; variant < 3; variant++) {
+        std::string raw = ">dense....\n" + std::string(53, '\n');
+        std::vector<uint64_t> lo, hi;
+        const std::string bodies = any_letters(256, 0, 5 + (uint32_t)variant);
+        for (int k = 0; k < 256; k++) {
+            lo.push_back(raw.size());
+            raw.push_back(variant == 2 && k % 7 == 3 ? "*-[`{@~"[k / 7 % 7] : bodies[(size_t)k]);
+            hi.push_back(raw.size());
+            raw.push_back(variant == 1 && k % 4 == 0 ? "*\x01\x80\xff"[k / 4 % 4] : '\n');
+        }
+        std::vector<uint8_t> alt(256);
+        for (size_t r = 0; r < 256; r++) alt[r] = (uint8_t)(r % 2);
+        for (int mode = 0; mode < 2; mode++) {
+            check_load_arrays(raw, lo, hi, &alt, mode, 0, "dense records, keep alternating");
+            check_load_arrays(raw, lo, hi, nullptr, mode, 0, "dense records");
+        }
+        if (variant == 2) {  // (a launch is 64 OS threads here: a batch each for the first 64 records only)
+            const std::vector<uint64_t> lo64(lo.begin(), lo.begin() + 64), hi64(hi.begin(), hi.begin() + 64);
+            check_load_arrays(raw, lo64, hi64, &alt, 1, 1, "dense records, a batch each");
+        }
+    }
+    // gather: the segment counts, the two ends of the bases, the two ends of the store
+    {
+        const std::string s0 = any_letters(kGroupSpan + 20, 0, 29), s1 = any_letters(333, 0, 31);
+        std::string raw = ">c0\n";
+        std::vector<uint64_t> lo, hi;
+        for (const std::string* s : {&s0, &s1}) {
+            if (s == &s1) raw += "\n>c1\n";
+            lo.push_back(raw.size());
+            for (size_t i = 0; i < s->size(); i += 70) { if (i) raw.push_back('\n'); raw += s->substr(i, 70); }
+            hi.push_back(raw.size());
+        }
+        raw.push_back('\n');
+        for (uint64_t budget : {(uint64_t)0, (uint64_t)1}) {
+            std::vector<Seg> segs;
+            for (uint32_t i = 0; i < 5000; i++) segs.push_back(Seg{0, (7 * i) % 16000, 1, 2 + 3ull * i, i % 8});
+            check_gather_arrays(raw, lo, hi, segs, 3 * 5000 + 8, budget, "5000 segments of one base");
+            for (uint32_t len : {kSpan, kGroupSpan}) {
+                segs.clear();
+                uint64_t d = 5;
+                uint32_t k = 0;
+                for (uint32_t flags : {0u, 1u, 7u}) { segs.push_back(Seg{0, k++, len, d, flags}); d += len + 9; }
+                check_gather_arrays(raw, lo, hi, segs, d + 16, budget, "spans that are one segment");
+            }
+            segs.clear();
+            uint64_t d = 0;
+            for (uint32_t flags : {0u, 1u, 3u})
+                for (uint32_t dm = 0; dm < 16; dm++)
+                    for (uint32_t len : {1u, 15u, 16u, 17u, 40u}) {
+                        d = ((d + 15) & ~15ull) + dm;
+                        segs.push_back(Seg{0, 0, len, d, flags});
+                        d += len;
+                        d = ((d + 15) & ~15ull) + dm;
+                        segs.push_back(Seg{1, (uint32_t)s1.size() - len, len, d, flags});
+                        d += len;
+                    }
+            check_gather_arrays(raw, lo, hi, segs, d + 20, budget, "the two ends of the bases");
+        }
+        for (uint32_t len : {1u, 17u, 40u})
+            for (uint32_t flags : {0u, 1u})
+                check_gather_arrays(raw, lo, hi, {Seg{1, 3, len, 0, flags}, Seg{1, 50, len, 203 - len, flags}}, 203, 0, "the two ends of the store");
+    }
+    return g_fail ? 1 : 0;
+}
+
 }  // namespace
 
 int main(int argc, char* argv[]) {
@@ -327,6 +574,7 @@ int main(int argc, char* argv[]) {
     if (argc >= 2 && !strcmp(argv[1], "synthesis")) return synthesis_main(argc - 1, argv + 1);
     if (argc >= 2 && !strcmp(argv[1], "preref")) return preref_main(argc - 1, argv + 1);
     if (argc >= 2 && !strcmp(argv[1], "seams")) return seams();
-    fprintf(stderr, "usage: refseq_check extract|synthesis|preref <the program's arguments> | seams\n");
+    if (argc >= 2 && !strcmp(argv[1], "limits")) return limits();
+    fprintf(stderr, "usage: refseq_check extract|synthesis|preref <the program's arguments> | seams | limits\n");
     return 2;
 }

@@ -209,3 +209,16 @@ def test_library_takes_the_knobs_as_strtoll_reads_them(monkeypatch):
     e = pytest.raises(capi.RsemHipError, lambda: ck.push(**ar.pack([])))
     assert e.value.status == INVALID and "RSEM_ALNCHECK_HASH_BITS" in str(e.value) and "from 1 to 64" in str(e.value)
     ck.close()
+
+
+@pytest.mark.parametrize("bad", ["99999999999999999999", "-99999999999999999999", "7x", "7 ", "", "0"])
+def test_library_refuses_what_is_no_whole_number_in_range(monkeypatch, bad):
+    """the reject side: a value strtoll clamps to the ends of long long, text behind the number, nothing, and 0 below lo = 1"""
+    from rsem_amd import capi
+    ck = capi.Alncheck([100, 50])
+    monkeypatch.setenv("RSEM_ALNCHECK_BATCH_ITEMS", bad)
+    e = pytest.raises(capi.RsemHipError, lambda: ck.push(**ar.pack([])))
+    assert e.value.status == INVALID and "RSEM_ALNCHECK_BATCH_ITEMS" in str(e.value)
+    e = pytest.raises(capi.RsemHipError, lambda: capi.alncheck_unique([0], b"\0", []))
+    assert e.value.status == INVALID and "RSEM_ALNCHECK_BATCH_ITEMS" in str(e.value)
+    ck.close()

@@ -243,3 +243,13 @@ def test_library_takes_the_batch_knob_as_strtoll_reads_it(monkeypatch):
         monkeypatch.setenv("RSEM_DEPTH_BATCH_ITEMS", good)
         got, info = capi.depth_accumulate(3, np.zeros(0, np.uint64), np.zeros(0, np.uint32), np.zeros(0))  # no block: no device needed
         assert len(got) == 3 and info["batch_items"] == 7 and info["n_batches"] == 0, good
+
+
+@pytest.mark.parametrize("bad", ["99999999999999999999", "-99999999999999999999", "7x", "7 ", "", "0"])
+def test_library_refuses_what_is_no_whole_number_in_range(monkeypatch, bad):
+    """the reject side: a value strtoll clamps to the ends of long long, text behind the number, nothing, and 0 below lo = 1"""
+    from rsem_amd import capi
+    monkeypatch.setenv("RSEM_DEPTH_BATCH_ITEMS", bad)
+    with pytest.raises(capi.RsemHipError) as e:
+        capi.depth_accumulate(3, np.zeros(0, np.uint64), np.zeros(0, np.uint32), np.zeros(0))
+    assert e.value.status == INVALID and "RSEM_DEPTH_BATCH_ITEMS" in str(e.value)

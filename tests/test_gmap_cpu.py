@@ -272,3 +272,15 @@ def test_library_takes_the_batch_knob_as_strtoll_reads_it(monkeypatch):
         o = g.convert(1, [0], [], [], [], [], [])  # nothing to convert: no device needed
         assert o["info"]["batch_items"] == 7 and o["info"]["n_batches"] == 0, good
     g.close()
+
+
+@pytest.mark.parametrize("bad", ["99999999999999999999", "-99999999999999999999", "7x", "7 ", "", "0"])
+def test_library_refuses_what_is_no_whole_number_in_range(monkeypatch, bad):
+    """the reject side: a value strtoll clamps to the ends of long long, text behind the number, nothing, and 0 below lo = 1"""
+    from rsem_amd import capi
+    g = small_gmap(capi)
+    monkeypatch.setenv("RSEM_GMAP_BATCH_ITEMS", bad)
+    with pytest.raises(capi.RsemHipError) as e:
+        g.convert(1, [0], [], [], [], [], [])
+    assert e.value.status == INVALID and "RSEM_GMAP_BATCH_ITEMS" in str(e.value)
+    g.close()

@@ -143,6 +143,122 @@ def test_check_program_sorts_by_a_workgroup_and_stops_without_a_partner(checker,
     assert r.returncode == 255 and r.stdout == b".\n" and r.stderr.startswith(b"Read lonely: ") and r.stderr.count(b"\n") == 1
 
 
+# ---- the limit inputs of tests/pairscan_limits.py on the emulator ------------------------------------------------------------------
+
+def emulate(checker, tmp_path, recs, env=None):
+    """the records through `pairscan_check records` (a file written here): the verdict, the counts and the permutation equal the
+    restatement's, and the sanitizers have nothing to say.  Returns (n_batches, n_sorted_groups)."""
+    path = os.path.join(str(tmp_path), "records.txt")
+    with open(path, "w") as f:
+        for r in recs:
+            f.write("%s %d %d %d %d\n" % (r.name.hex(), r.flag, r.tid, r.pos, r.mpos))
+    e = dict(os.environ, **(env or {}))
+    if env is None:
+        e.pop("RSEM_PAIRSCAN_BATCH_ITEMS", None)
+    r = subprocess.run([checker, "records", path], capture_output=True, text=True, env=e)
+    assert r.returncode == 0 and r.stderr == "", r.stderr[-3000:]
+    lines = r.stdout.split("\n")
+    code, group, group_record, n_groups, n_batches, n_sorted = (int(x) for x in lines[0].split())
+    want_perm, want, _ = pr.reorder(recs)
+    assert pr.Verdict(code, group, group_record) == want
+    if want.code == pr.OK:
+        assert [int(x) for x in lines[1:] if x] == want_perm and n_groups == len(pr.walk(recs))
+    return n_batches, n_sorted
+
+
+def test_check_program_on_every_flag_byte(checker, tmp_path):
+    """the sweep of tests/test_pairscan_limits_gpu.py without the two high bits"""
+    import pairscan_limits as pl
+    ok, failing = pl.split_flag_groups(high_bits=(0,))
+    paired = [g for g in ok if g[0].flag & 1]
+    assert {pr.class_of(r.flag) for g in paired for r in g[1:]} == {0, 1, 2, 3} and {r.flag for g in ok for r in g[1:]} == set(range(256))
+    both = [r for g in paired for r in g if pr.class_of(r.flag) == 0]
+    assert {(bool(r.flag & 0x40), pr.key(r)[3]) for r in both} == {(True, 0), (True, 1), (False, 0), (False, 1)}
+    recs, starts = pl.on_the_seams(ok)
+    assert {s % 256 for s in starts} >= {0, 63, 64, 255} and 256 in starts
+    emulate(checker, tmp_path, recs)
+    codes = [pr.reorder(g)[1].code for g in failing]
+    assert set(codes) == set(pl.FAIL_CODES) and len(failing) <= 64
+    filler = sum(ok[:90], [])
+    for g, code in zip(failing, codes):
+        assert pr.reorder(filler + g)[1] == pr.Verdict(code, len(pr.walk(filler)), len(filler))
+        emulate(checker, tmp_path, filler + g + pl.singles(3, "t%d"))
+
+
+@pytest.mark.parametrize("budget", [None, "300"])
+def test_check_program_on_groups_of_whole_tiles(checker, tmp_path, budget):
+    """510, 512, 514 and 1024 records with the tie structure, 1024 equal ones and 1024 descending ones (the group of 4096 is the GPU's)"""
+    import pairscan_limits as pl
+    recs, where = pl.big_stream(sizes=pl.BIG_SIZES[:4])
+    want = pr.reorder(recs)[0]
+    first, n = where[4]
+    assert n == 1024 and want[first:first + n] == list(range(first, first + n))
+    n_batches, n_sorted = emulate(checker, tmp_path, recs, {"RSEM_PAIRSCAN_BATCH_ITEMS": budget} if budget else None)
+    assert n_sorted == len(where) == 6 and n_batches == pr.expected_batches(recs, int(budget) if budget else pr.DEFAULT_BATCH_ITEMS)
+
+
+def test_check_program_on_partial_groups_of_four_tiles(checker, tmp_path):
+    import pairscan_limits as pl
+    from test_pairscan_gpu import partial_group, shape
+    even = []
+    for k, (size, diff, swap) in enumerate([(1022, 0, False), (1024, 1, True), (1026, 21, False), (1024, 21, True)]):
+        even += partial_group("e%d" % k, *shape(size, diff, swap), n_both=(k % 3) * 2) + pl.singles(k % 2, "t%d_" + str(k))
+    assert pr.reorder(even)[1].code == pr.OK
+    emulate(checker, tmp_path, even)
+    for size in (1023, 1025):
+        n1, n2, nu = shape(size - 1, 1, False)
+        recs = pl.singles(5) + partial_group("o", n1, n2, nu + 1, n_both=4) + pl.singles(2, "b%d")
+        assert pr.reorder(recs)[1] == pr.Verdict(pr.ODD_PARTIAL, 5, 5)
+        emulate(checker, tmp_path, recs)
+
+
+def test_check_program_on_keys_at_the_ends_of_32_bits(checker, tmp_path):
+    import pairscan_limits as pl
+    sub = pl.end_keys_subset()
+    assert pr.reorder(sub)[0] == [3, 4, 0, 6, 5, 1, 7, 2]
+    emulate(checker, tmp_path, sub + pl.singles(3))
+    n_batches, n_sorted = emulate(checker, tmp_path, pl.singles(60) + pl.end_keys_group() + pl.singles(3, "t%d"))
+    assert n_sorted == 1
+
+
+def test_check_program_on_names_at_their_limits(checker, tmp_path):
+    """names of 254 bytes, of canonical length 0, a prefix for a neighbour, a NUL inside: on the lanes 0, 63 | 64 and 255 | 256 and at
+    the edges of batches of 1 and 7"""
+    import pairscan_limits as pl
+    for kind in sorted(pl.name_blocks()):
+        for at in (0, 63, 255):
+            recs = pl.name_stream(kind, at)
+            assert pr.reorder(recs)[0] != list(range(len(recs)))
+            emulate(checker, tmp_path, recs)
+        for budget in (1, 7):
+            recs = pl.name_stream(kind, 3)
+            n_batches, _ = emulate(checker, tmp_path, recs, {"RSEM_PAIRSCAN_BATCH_ITEMS": str(budget)})
+            assert n_batches == pr.expected_batches(recs, budget)
+
+
+def test_check_program_on_names_of_254_bytes_in_a_file(checker, tmp_path):
+    """the same names through the program's own reader and writer (a NUL inside a name is not something a file carries)"""
+    import pairscan_limits as pl
+    d = str(tmp_path)
+    recs = sum((pl.name_stream(kind, at) for kind, at in (("last_byte", 0), ("behind_the_space", 63), ("prefix", 2))), [])
+    for k, r in enumerate(recs):  # one stream: the fillers' names must not repeat
+        if r.name[:1] in (b"u", b"t"):
+            recs[k] = r._replace(name=r.name + b"_%d" % k)
+    pr.write_bam(os.path.join(d, "in.bam"), recs, block=4000)
+    for env in KNOBS:
+        r = subprocess.run([checker, "2", "in.bam", "out.bam"], capture_output=True, cwd=d, env=dict(os.environ, **env))
+        assert (r.returncode, r.stdout, r.stderr) == (0, b".\nFinished!\n", b""), r.stderr[-2000:]
+        assert gr.bgzf_inflate(open(os.path.join(d, "out.bam"), "rb").read()) == pr.scan(os.path.join(d, "in.bam"))[3]
+
+
+@pytest.mark.parametrize("n_small,n_large", [(1, 0), (4, 0), (5, 0), (0, 3), (0, 0)])
+def test_check_program_on_lists_of_groups_to_sort(checker, tmp_path, n_small, n_large):
+    import pairscan_limits as pl
+    recs = pl.list_stream(n_small, n_large)
+    _, n_sorted = emulate(checker, tmp_path, recs)
+    assert n_sorted == n_small + n_large
+
+
 # ---- the program, before it needs a device ---------------------------------------------------------------------------------------
 
 @pytest.fixture(scope="module")
@@ -223,6 +339,17 @@ def test_library_takes_the_batch_knob_as_strtoll_reads_it(monkeypatch):
         monkeypatch.setenv("RSEM_PAIRSCAN_BATCH_ITEMS", good)
         perm, v = ps.reorder(**pr.pack([]))  # nothing to order: no device needed
         assert len(perm) == 0 and v["batch_items"] == 7, good
+    ps.close()
+
+
+@pytest.mark.parametrize("bad", ["99999999999999999999", "-99999999999999999999", "7x", "7 ", "", "0"])
+def test_library_refuses_what_is_no_whole_number_in_range(monkeypatch, bad):
+    """the reject side: a value strtoll clamps to the ends of long long, text behind the number, nothing, and 0 below lo = 1"""
+    from rsem_amd import capi
+    ps = capi.Pairscan()
+    monkeypatch.setenv("RSEM_PAIRSCAN_BATCH_ITEMS", bad)
+    e = pytest.raises(capi.RsemHipError, lambda: ps.reorder(**pr.pack([])))
+    assert e.value.status == INVALID and "RSEM_PAIRSCAN_BATCH_ITEMS" in str(e.value)
     ps.close()
 
 

@@ -102,6 +102,14 @@ def test_kernel_bodies_at_their_seams(checker, tmp_path):
     assert r.stderr == b""
 
 
+def test_kernel_bodies_at_their_limits(checker, tmp_path):
+    """the shapes of tests/refseq_limits.py restated in the check program: every byte value in both modes and under the flag sets 0..7,
+    bodies of no byte and bodies that touch, eight records in a chunk, 5000 segments, the two ends of the bases and of the store"""
+    r = run_in(str(tmp_path), [checker, "limits"])
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert r.stderr == b""
+
+
 USAGE = {"extract": b"Usage: rsem-extract-reference-transcripts refName quiet gtfF sources hasMappingFile [mappingFile] chromosome_file_1 [chromosome_file_2 ...]\n",
          "synthesis": b"Usage: synthesisRef refName quiet hasMappingFile<0,no;1,yes;2,allele-specific> [mappingFile] reference_file_1 [reference_file_2 ...]\n",
          "preref": b"USAGE : rsem-preref refFastaF polyAChoice refName [-l polyALen] [-f exceptionF] [-q]\n\n"}
