@@ -738,6 +738,98 @@ int rsem_pairscan_reorder(rsem_pairscan* h, int64_t n_records, const uint64_t* n
                           rsem_pairscan_verdict* v);
 void rsem_pairscan_destroy(rsem_pairscan* h);
 
+/* ---- reads drawn from the read model (rsem-simulate-reads) ---------------------------------------------------------------------------
+ * A handle holds one model after startSimulation (SingleModel.h:399-411, SingleQModel.h:413-426, PairedEndModel.h:358-370,
+ * PairedEndQModel.h:371-384) on one device: every table a RUNNING SUM as the reference builds it -- theta (theta_cdf), the length
+ * distributions (LenDist.h: cdf[0 .. span], cdf[0] = 0), QualDist.h:116-130 (qc_init, qc_trans), the profile with its all-zero rows
+ * repaired (QProfile.h:151-193, Profile.h:163-205), the noise profile (NoiseQProfile.h:153-166, NoiseProfile.h:137-144) -- the
+ * RSPD's pdf and cdf of B + 2 entries (RSPD.h:182-193 is evaluated in place, not tabulated), and the transcripts' forward strands,
+ * poly(A) tails included, with their two lengths.  Index 0 of the per-transcript arrays is unused.
+ * A batch replaces the loop of simulation.cpp:121-126: per read, model.simulate repeated until it gives a read.  An attempt is a fixed
+ * program of uniforms (rsem_amd/csrc/simulate_block.hpp); uniform k of an attempt is 32-bit word k of its source times 2^-32.
+ *   rsem_sim_counter_batch     word k of attempt a of read r: word k % 4 of Philox4x32-10 keyed (seed low, seed high) at counter (r low,
+ *                              r high, a, k / 4).  Reads first_read .. first_read + n_reads - 1: a pure function of seed and read.
+ *   rsem_sim_reference_begin   seeds boost::random::mt19937 as simul.h:11 does;
+ *   rsem_sim_reference_batch   the next up to max_reads reads of that ONE stream, in stream order: the reads, and through them every file
+ *                              of the program, are the reference's for the same seed.  The stream is searched in chunks: an attempt is tried
+ *                              at EVERY word of a chunk, then the words the stream really visits are found (tiles, a hop, a prefix sum).
+ * Both fill the caller's arrays for reads 0 .. n_reads - 1 of the batch: sid, dir, pos, insert_l, len1, len2, the failed attempts
+ * before the read (attempts), and the letters and qualities (value + 33) of read i at byte i * stride of seq1, qual1, seq2, qual2.  A
+ * model without qualities leaves qual1 / qual2 alone, a single-end one seq2 / qual2 and len2 (0).  The handle adds the reads to its
+ * per-transcript counts (simulation.cpp:124) and the failed attempts to its total (:122).
+ * status: RSEM_SIM_ATTEMPT_CAP: a read failed the cap's number of attempts (2^20; the reference would go on for ever);
+ * RSEM_SIM_SHORT_INSERT: a paired-end insert shorter than every mate length (PairedEndQModel.h:415-417 goes on with a length of -1);
+ * RSEM_SIM_PAST_PROFILE: a read longer than the no-quality profile (Profile.h:211 reads past its table); RSEM_SIM_QUALITY_RANGE: a
+ * quality above 93 was drawn (the tables have 100 rows; the reference ends at the assertion of QProfile.h:40).  With status != 0 the batch's
+ * arrays are unspecified, nothing is added to the counts and the handle takes no more batches (RSEM_ERR_STATE).
+ * Checked before a device is touched (RSEM_ERR_INVALID): NULL pointers, a type outside 0..3, M < 1, tables that a model of the type
+ * needs and that are NULL, lengths that do not fit (lb < ub, 1 <= full_len <= tot_len, seq_off ascending by tot_len at least), running
+ * sums that descend or are not finite, a batch whose capacity is below the reads asked for or whose stride is below the longest read.
+ * Knobs (environment, whole numbers, read at every call, anything else: RSEM_ERR_INVALID; the reads do not depend on them):
+ * RSEM_SIM_BATCH_READS (2^18) the reads the program asks for at a time, RSEM_SIM_CHUNK_WORDS (2^22) the words of a chunk,
+ * RSEM_SIM_TILE (2048, at most 8192) the positions of a tile, RSEM_SIM_ATTEMPT_CAP (2^20), RSEM_SIM_LDS_TABLES (1) the quality tables
+ * in LDS (1) or read through the caches (0). */
+#define RSEM_SIM_OK 0
+#define RSEM_SIM_ATTEMPT_CAP 1
+#define RSEM_SIM_SHORT_INSERT 2
+#define RSEM_SIM_PAST_PROFILE 3
+#define RSEM_SIM_QUALITY_RANGE 4
+typedef struct rsem_sim rsem_sim;
+typedef struct rsem_sim_model {
+    int32_t type;               /* 0 Single, 1 SingleQ, 2 PairedEnd, 3 PairedEndQ */
+    int32_t M;
+    int32_t has_mld;            /* single-end: m_cdf is given; paired-end: must be 1 */
+    int32_t est_rspd, B;
+    int32_t pro_len;            /* no-quality models: positions of pc */
+    int32_t g_lb, g_ub, m_lb, m_ub;
+    double prob_f;              /* Orientation.h:36 */
+    const double* theta_cdf;    /* M + 1 */
+    const int32_t* full_len;    /* M + 1 */
+    const int32_t* tot_len;     /* M + 1 */
+    const uint64_t* seq_off;    /* M + 2 */
+    const uint8_t* seq;         /* seq_off[M + 1] bytes */
+    const double* g_cdf;        /* g_ub - g_lb + 1 */
+    const double* m_cdf;        /* m_ub - m_lb + 1, or NULL */
+    const double* r_pdf;        /* B + 2 (est_rspd only) */
+    const double* r_cdf;
+    const double* qc_init;      /* 100 (quality models only) */
+    const double* qc_trans;     /* 100 * 100 */
+    const double* pc;           /* 100 * 25, or pro_len * 25 */
+    const double* npc;          /* 100 * 5, or 5 */
+} rsem_sim_model;
+typedef struct rsem_sim_batch {
+    int64_t capacity;           /* in: reads the arrays hold */
+    int32_t stride;             /* in: bytes a read in seq1, qual1, seq2, qual2 */
+    int32_t status;             /* RSEM_SIM_* */
+    int64_t n_reads;            /* reads in the arrays */
+    uint64_t resimulations;     /* failed attempts of this batch */
+    int32_t *sid, *dir, *pos, *insert_l, *len1, *len2;
+    uint32_t* attempts;
+    uint8_t *seq1, *qual1, *seq2, *qual2;
+    int32_t n_chunks;           /* reference stream: chunks searched */
+    int32_t n_launches;
+    uint64_t stream_words;      /* reference stream: generator words the batch consumed */
+    uint64_t device_bytes;
+    double words_ms;            /* host: the generator */
+    double upload_ms;           /* device, by events: the words going up */
+    double search_ms;           /* device: an attempt's header at every word, tiles, hop, marks, prefix sum */
+    double body_ms;             /* device: the reads */
+    double download_ms;         /* host clock: the arrays coming back */
+} rsem_sim_batch;
+typedef struct rsem_sim_knobs {
+    uint64_t batch_reads, chunk_words, tile, attempt_cap, lds_tables;
+} rsem_sim_knobs;
+int rsem_sim_read_knobs(rsem_sim_knobs* k);
+/* the longest read of the model and whether every sample() of it takes one uniform (what the search of the reference stream can skip) */
+int rsem_sim_create(rsem_sim** out, const rsem_sim_model* m, int device);
+int rsem_sim_info(const rsem_sim* h, int32_t* max_len, int32_t* plain);
+int rsem_sim_counter_batch(rsem_sim* h, uint64_t seed, uint64_t first_read, int64_t n_reads, rsem_sim_batch* b);
+int rsem_sim_reference_begin(rsem_sim* h, uint32_t seed);
+int rsem_sim_reference_batch(rsem_sim* h, int64_t max_reads, rsem_sim_batch* b);
+/* counts: M + 1 (simulation.cpp:124); resimulations: the total of :122 */
+int rsem_sim_totals(rsem_sim* h, uint64_t* counts, uint64_t* resimulations);
+void rsem_sim_destroy(rsem_sim* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,7 @@ LIB = os.path.join(HERE, "librsem_hip.so")
 BIN = os.path.join(HERE, "bin")
 
 HIP_SOURCES = ["status.hip", "comm.hip", "em.hip", "gibbs.hip", "gibbs_diag.hip", "model.hip", "ci.hip", "kmer.hip", "depth.hip", "gmap.hip", "refseq.hip",
-               "alncheck.hip", "pairscan.hip"]
+               "alncheck.hip", "pairscan.hip", "simulate.hip"]
 HOST_PROGRAMS = {"rsem-run-em": ["host/run_em.cpp"], "rsem-run-gibbs": ["host/run_gibbs.cpp"],
                  "rsem-calculate-credibility-intervals": ["host/calc_ci.cpp"],
                  "rsem-for-ebseq-calculate-clustering-info": ["host/calc_clustering_info.cpp"],
@@ -20,7 +20,8 @@ HOST_PROGRAMS = {"rsem-run-em": ["host/run_em.cpp"], "rsem-run-gibbs": ["host/ru
                  "rsem-synthesis-reference-transcripts": ["host/synthesis_reference.cpp"],
                  "rsem-preref": ["host/preref.cpp"],
                  "rsem-sam-validator": ["host/sam_validator.cpp"], "rsem-get-unique": ["host/get_unique.cpp"],
-                 "rsem-scan-for-paired-end-reads": ["host/scan_for_paired_end_reads.cpp"]}
+                 "rsem-scan-for-paired-end-reads": ["host/scan_for_paired_end_reads.cpp"],
+                 "rsem-simulate-reads": ["host/simulate_reads.cpp"]}
 # stages around the hot path that never touch the GPU: plain g++, no librsem_hip dependency
 HOST_ONLY_PROGRAMS = {"rsem-parse-alignments": ["host/parse_alignments.cpp"]}
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",

@@ -86,6 +86,23 @@ class PairscanVerdict(C.Structure):
                 ("upload_ms", C.c_double), ("kernel_ms", C.c_double)]
 
 
+class SimModel(C.Structure):
+    _fields_ = [("type", C.c_int32), ("M", C.c_int32), ("has_mld", C.c_int32), ("est_rspd", C.c_int32), ("B", C.c_int32), ("pro_len", C.c_int32), ("g_lb", C.c_int32),
+                ("g_ub", C.c_int32), ("m_lb", C.c_int32), ("m_ub", C.c_int32), ("prob_f", C.c_double)] + [
+        (n, C.c_void_p) for n in ("theta_cdf", "full_len", "tot_len", "seq_off", "seq", "g_cdf", "m_cdf", "r_pdf", "r_cdf", "qc_init", "qc_trans", "pc", "npc")]
+
+
+class SimBatch(C.Structure):
+    _fields_ = [("capacity", C.c_int64), ("stride", C.c_int32), ("status", C.c_int32), ("n_reads", C.c_int64), ("resimulations", C.c_uint64)] + [
+        (n, C.c_void_p) for n in ("sid", "dir", "pos", "insert_l", "len1", "len2", "attempts", "seq1", "qual1", "seq2", "qual2")] + [
+        ("n_chunks", C.c_int32), ("n_launches", C.c_int32), ("stream_words", C.c_uint64), ("device_bytes", C.c_uint64), ("words_ms", C.c_double),
+        ("upload_ms", C.c_double), ("search_ms", C.c_double), ("body_ms", C.c_double), ("download_ms", C.c_double)]
+
+
+class SimKnobs(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("batch_reads", "chunk_words", "tile", "attempt_cap", "lds_tables")]
+
+
 class EmProfile(C.Structure):
     _fields_ = [("total_ms", C.c_double), ("estep_ms_sum", C.c_double), ("estep_launches", C.c_int32),
                 ("rounds", C.c_int32), ("algorithmic_bytes_per_round", C.c_uint64)]
@@ -176,6 +193,15 @@ def lib():
         L.rsem_pairscan_reorder.argtypes = [vp, C.c_int64] + [vp] * 6 + [i32, vp, vp]
         L.rsem_pairscan_destroy.argtypes = [vp]
         L.rsem_pairscan_destroy.restype = None
+        L.rsem_sim_read_knobs.argtypes = [vp]
+        L.rsem_sim_create.argtypes = [C.POINTER(vp), vp, ci]
+        L.rsem_sim_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+        L.rsem_sim_counter_batch.argtypes = [vp, u64, u64, C.c_int64, vp]
+        L.rsem_sim_reference_begin.argtypes = [vp, C.c_uint32]
+        L.rsem_sim_reference_batch.argtypes = [vp, C.c_int64, vp]
+        L.rsem_sim_totals.argtypes = [vp, _u64p, C.POINTER(u64)]
+        L.rsem_sim_destroy.argtypes = [vp]
+        L.rsem_sim_destroy.restype = None
         _lib = L
     return _lib
 
@@ -783,6 +809,90 @@ class Pairscan:
     def close(self):
         if self.h:
             lib().rsem_pairscan_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+SIM_OK, SIM_ATTEMPT_CAP, SIM_SHORT_INSERT, SIM_PAST_PROFILE, SIM_QUALITY_RANGE = range(5)
+
+
+def sim_knobs():
+    """the RSEM_SIM_* knobs in force (rsem_sim_read_knobs)"""
+    k = SimKnobs()
+    _check(lib().rsem_sim_read_knobs(C.addressof(k)))
+    return {f: getattr(k, f) for f, _ in SimKnobs._fields_}
+
+
+class Simulate:
+    """rsem_sim: reads drawn from a read model after startSimulation.  tables: a dict with type, prob_f, theta_cdf, full_len, tot_len
+    (index 0 unused), seqs (a list of M + 1 strings or bytes, [0] unused), g_lb, g_ub, g_cdf and, where the model has them, m_lb, m_ub,
+    m_cdf, est_rspd with r_pdf and r_cdf (B + 2 entries), qc_init, qc_trans, pc, npc -- every table a running sum, flat or nested."""
+
+    def __init__(self, tables, device=0):
+        t = tables
+        f64 = lambda k: None if t.get(k) is None else np.ascontiguousarray(np.asarray(t[k], np.float64).reshape(-1))  # noqa: E731
+        self.M = len(t["full_len"]) - 1
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in t["seqs"]]
+        off = np.zeros(self.M + 2, np.uint64)
+        off[1:] = np.cumsum([0] + [len(s) for s in seqs[1:]])
+        keep = {"theta_cdf": f64("theta_cdf"), "full_len": np.ascontiguousarray(t["full_len"], np.int32), "tot_len": np.ascontiguousarray(t["tot_len"], np.int32), "seq_off": off,
+                "seq": np.frombuffer(b"".join(seqs[1:]) or b"N", np.uint8), "g_cdf": f64("g_cdf"), "m_cdf": f64("m_cdf"), "r_pdf": f64("r_pdf"), "r_cdf": f64("r_cdf"),
+                "qc_init": f64("qc_init"), "qc_trans": f64("qc_trans"), "pc": f64("pc"), "npc": f64("npc")}
+        self.type = int(t["type"])
+        m = SimModel(type=self.type, M=self.M, has_mld=0 if t.get("m_cdf") is None else 1, est_rspd=1 if t.get("est_rspd") else 0, B=len(keep["r_pdf"]) - 2 if t.get("est_rspd") else 0,
+                     pro_len=0 if self.type in (1, 3) else len(keep["pc"]) // 25, g_lb=t["g_lb"], g_ub=t["g_ub"], m_lb=t.get("m_lb", 0), m_ub=t.get("m_ub", 1), prob_f=t["prob_f"])
+        for k, a in keep.items():
+            setattr(m, k, None if a is None else a.ctypes.data)
+        self.h = C.c_void_p()
+        _check(lib().rsem_sim_create(C.byref(self.h), C.addressof(m), device))
+        ml, plain = C.c_int32(), C.c_int32()
+        _check(lib().rsem_sim_info(self.h, C.byref(ml), C.byref(plain)))
+        self.max_len, self.plain = ml.value, bool(plain.value)
+
+    def _batch(self, n):
+        st = max(self.max_len, 1)
+        a = {k: np.zeros(max(n, 1), np.int32) for k in ("sid", "dir", "pos", "insert_l", "len1", "len2")}
+        a["attempts"] = np.zeros(max(n, 1), np.uint32)
+        for k in ("seq1", "qual1", "seq2", "qual2"):
+            a[k] = np.zeros((max(n, 1), st), np.uint8)
+        b = SimBatch(capacity=n, stride=st)
+        for k, v in a.items():
+            setattr(b, k, v.ctypes.data)
+        return a, b
+
+    def _result(self, a, b):
+        out = {f: getattr(b, f) for f, _ in SimBatch._fields_ if f not in a}
+        n = b.n_reads
+        out.update({k: v[:n] for k, v in a.items()})
+        return out
+
+    def counter_batch(self, seed, first_read, n_reads):
+        """rsem_sim_counter_batch -> a dict of the batch's arrays (cut to n_reads) and scalars"""
+        a, b = self._batch(n_reads)
+        _check(lib().rsem_sim_counter_batch(self.h, seed, first_read, n_reads, C.addressof(b)))
+        return self._result(a, b)
+
+    def reference_begin(self, seed):
+        _check(lib().rsem_sim_reference_begin(self.h, seed))
+
+    def reference_batch(self, max_reads):
+        a, b = self._batch(max_reads)
+        _check(lib().rsem_sim_reference_batch(self.h, max_reads, C.addressof(b)))
+        return self._result(a, b)
+
+    def totals(self):
+        counts, resim = np.zeros(self.M + 1, np.uint64), C.c_uint64()
+        _check(lib().rsem_sim_totals(self.h, counts, C.byref(resim)))
+        return counts, resim.value
+
+    def close(self):
+        if self.h:
+            lib().rsem_sim_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

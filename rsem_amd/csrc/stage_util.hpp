@@ -1,4 +1,4 @@
-// stage_util.hpp -- the host-side scaffolding the batch stages share (kmer, depth, gmap, refseq, alncheck, pairscan, ci,
+// stage_util.hpp -- the host-side scaffolding the batch stages share (kmer, depth, gmap, refseq, alncheck, pairscan, simulate, ci,
 // gibbs_diag): device memory that is released on every path, buffers that grow, a stream with the three
 // events around a batch's upload and its kernels, the whole-number knobs.  Nothing here launches a kernel.
 #pragma once

@@ -1,8 +1,8 @@
 #!/bin/bash
 # An RSEM installation directory in which some programs are the drop-ins of this repo.
 #   tools/make_overlay.sh <rsem_dir> <out_dir> [program ... | --none]      default programs: the four pipeline drop-ins, rsem-tbam2gbam, rsem-bam2wig, rsem-bam2readdepth
-#                                                                           the three reference-preparation programs, rsem-sam-validator, rsem-get-unique and
-#                                                                           rsem-scan-for-paired-end-reads
+#                                                                           the three reference-preparation programs, rsem-sam-validator, rsem-get-unique,
+#                                                                           rsem-scan-for-paired-end-reads and rsem-simulate-reads
 # rsem-calculate-expression, rsem-prepare-reference, convert-sam-for-rsem and rsem-plot-transcript-wiggles each put THEIR OWN
 # directory first in PATH (rsem-calculate-expression:12, convert-sam-for-rsem:7-12: FindBin::RealBin, symlinks resolved) and run bare
 # program names, so a drop-in has to sit next to the driver: <out_dir> gets COPIES of these four Perl scripts and of the *.pm
@@ -12,7 +12,7 @@
 set -e
 src=$(cd "$1" && pwd); out=$2; shift 2
 here=$(cd "$(dirname "$0")/.." && pwd)
-progs=("$@"); [ ${#progs[@]} -eq 0 ] && progs=(rsem-parse-alignments rsem-run-em rsem-run-gibbs rsem-calculate-credibility-intervals rsem-tbam2gbam rsem-bam2wig rsem-bam2readdepth rsem-extract-reference-transcripts rsem-synthesis-reference-transcripts rsem-preref rsem-sam-validator rsem-get-unique rsem-scan-for-paired-end-reads)
+progs=("$@"); [ ${#progs[@]} -eq 0 ] && progs=(rsem-parse-alignments rsem-run-em rsem-run-gibbs rsem-calculate-credibility-intervals rsem-tbam2gbam rsem-bam2wig rsem-bam2readdepth rsem-extract-reference-transcripts rsem-synthesis-reference-transcripts rsem-preref rsem-sam-validator rsem-get-unique rsem-scan-for-paired-end-reads rsem-simulate-reads)
 [ "${progs[0]}" == "--none" ] && progs=()
 mkdir -p "$out"
 for f in "$src"/*; do
